@@ -3,6 +3,7 @@
 semantics, bit-exact) on synthetic 600x1000x3 uint8 images resident in HBM.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--op gauss5|gauss3|box3|...]
+                  [--dump-outputs DIR] [--full]
 
 One step = one pass of the filter over one batch of B images (default 256, BASELINE config 2's
 batch with the metric's 5x5 Gaussian).  For N > 1 the driver launches one process per GPU
@@ -10,7 +11,17 @@ batch with the metric's 5x5 Gaussian).  For N > 1 the driver launches one proces
 independent: no collective in the timed region), the timed region is bracketed by
 barrier + synchronize and the max over ranks is reported.  Rank 0 prints ONE JSON line with the
 roofline object of the dominant kernel (algorithmic 6 B/pixel over the HIP-event-timed launch
-duration) and the CPU baseline (oracle C restatement of the same filter, OpenMP, bounded sample).
+duration of the K timed steps).
+
+A plain run sets up, warms up, times the K steps, writes its outputs if --dump-outputs is given and
+prints the line.  --full adds the legs that take runs of their own: the CPU baseline (oracle C
+restatement of the same filter, OpenMP, bounded sample; --no-cpu skips it), the same-run copy
+ceiling (--no-copy skips it) and the per-launch event-pair median.
+
+--dump-outputs DIR writes what the last timed step computed (the arrays the caller of the op
+receives) as DIR/<name>.npy, float32 or float64, at most 64 MB in all: an output over its share
+is a fixed, seeded sample of its elements.  The batch and every noise stream are seeded, so two
+runs with the same arguments see the same inputs.
 """
 from __future__ import annotations
 
@@ -255,7 +266,7 @@ def _detect_e2e(idn, x, y):
     from idn import detect_blob
     im = detect_blob.apply_noise(st["path"], "gaussian_wavelet_var0.1", mode="test_v0",
                                  decode="gpu", as_tensor=True)
-    detect_blob._get_blobs(im)
+    st["last"] = detect_blob._get_blobs(im)
 
 
 OPS["detect_e2e"] = ("per-image test_net body: JPEG -> gaussian_wavelet (test_v0) -> blob, numpy out",
@@ -287,7 +298,7 @@ def _detect_e2e_pipelined(idn, x, y):
     from idn import detect_blob
     im = detect_blob.apply_noise(st["reader"][st["k"]], "gaussian_wavelet_var0.1", mode="test_v0",
                                  decode="gpu", as_tensor=True)
-    detect_blob._get_blobs(im)
+    st["last"] = detect_blob._get_blobs(im)
     st["k"] += 1
 
 
@@ -312,6 +323,40 @@ def synth_batch(torch, n, dev, seed=3):
         u = torch.rand((m, H, W, C), generator=g, device=dev) * 64 - 32
         out[i:i + m] = (base + u).clamp_(0, 255).to(torch.uint8)
     return out
+
+
+DUMP_BUDGET = 48 << 20  # bytes of .npy payload in all (the limit is 64 MB)
+
+
+def step_outputs(op, y):
+    """name -> array of what the op's last step handed its caller."""
+    if op == "gauss5_blob":
+        return {"blob": _gauss5_blob.__dict__["blob"]}
+    if op in ("detect_e2e", "detect_e2e_pipelined"):
+        blobs, scales = OPS[op][1].__dict__["last"]
+        return {"data": blobs["data"], "im_scale_factors": scales}
+    return {"out": y}
+
+
+def snapshot_outputs(torch, outs):
+    """Host copies of the outputs as float32 (float64 stays float64), each within its share of
+    DUMP_BUDGET: a larger one is sampled at sorted flat indices drawn from a fixed seed."""
+    import numpy as np
+    share = DUMP_BUDGET // max(1, len(outs))
+    snap = {}
+    for name, a in outs.items():
+        t = a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))
+        t = t.reshape(-1)
+        wide = t.dtype == torch.float64
+        n = share // (8 if wide else 4)
+        if t.numel() > n:
+            idx = np.sort(np.random.RandomState(20240607).randint(0, t.numel(), size=n,
+                                                                  dtype=np.int64))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        else:
+            t = t.reshape(a.shape)
+        snap[name] = t.to(torch.float64 if wide else torch.float32).cpu().numpy()
+    return snap
 
 
 def cpu_baseline(op: str, budget_s: float = 12.0):
@@ -518,8 +563,14 @@ def parse_args(argv=None):
                          "of sustained load have passed: the GPU's power controller settles the "
                          "clocks of a power-capped kernel over the first ~30-50 ms "
                          "(profiles/r02/clock/), and the timed K steps should see that steady state")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
-    ap.add_argument("--no-copy", action="store_true", help="skip the same-run copy ceiling")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs that take runs of their own: the CPU baseline, the "
+                         "same-run copy ceiling and the per-launch event-pair median")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline leg")
+    ap.add_argument("--no-copy", action="store_true", help="--full: skip the same-run copy ceiling")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 or "
+                         "float64, at most 64 MB in all; larger outputs as a fixed seeded sample)")
     ap.add_argument("--gather", action="store_true",
                     help="N>1: also time reassembling the filtered batch on every rank with one "
                          "RCCL all-gather over xGMI per step (reported as 'allgather')")
@@ -527,7 +578,10 @@ def parse_args(argv=None):
                     help="tools only: run through the tuning build (knobs from the environment)")
     ap.add_argument("--dry-run", action="store_true",
                     help="resolve ranks and shards and print them without touching a GPU (tests)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def copy_ceiling(idn, torch, x, y, reps: int = 20):
@@ -629,6 +683,11 @@ def main():
     # (region / K); event pairs around every launch add their own dispatch gaps (~2-4 us, a few
     # % of a 0.17 ms kernel) -- those are kept for the median only
     e_beg, e_end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    # the detect_e2e bodies draw their noise level from the global `random` stream, as the
+    # reference does; the settle loop above runs a time-bounded number of steps, so the stream is
+    # restarted here and the timed steps draw the same levels in every run
+    import random
+    random.seed(3)
     barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -641,14 +700,22 @@ def main():
     t1 = time.perf_counter()
     wall = t1 - t0
     avg_kern_ms = e_beg.elapsed_time(e_end) / args.steps
-    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-          for _ in range(min(args.steps, 10))]
-    for a, b in ev:  # untimed by the wall clock: per-launch pairs for the median
-        a.record(stream)
-        call(idn, x, y)
-        b.record(stream)
-    torch.cuda.synchronize()
-    kern_ms = sorted(a.elapsed_time(b) for a, b in ev)
+    if args.dump_outputs:  # the last timed step's outputs, before any later leg overwrites them
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, arr in snapshot_outputs(torch, step_outputs(args.op, y)).items():
+            np.save(os.path.join(args.dump_outputs,
+                                 name + (f".rank{rank}" if rank else "") + ".npy"), arr)
+    kern_ms = None
+    if args.full:
+        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+              for _ in range(min(args.steps, 10))]
+        for a, b in ev:  # untimed by the wall clock: per-launch pairs for the median
+            a.record(stream)
+            call(idn, x, y)
+            b.record(stream)
+        torch.cuda.synchronize()
+        kern_ms = sorted(a.elapsed_time(b) for a, b in ev)
 
     if world > 1:
         t = torch.tensor([wall], device=dev, dtype=torch.float64)
@@ -679,7 +746,7 @@ def main():
                   "algbw_GBps": round(y.numel() * (world - 1) / (g_ms * 1e-3) / 1e9, 1)}
 
     ceiling = None
-    if not args.no_copy and rank == 0:
+    if args.full and not args.no_copy and rank == 0:
         ceiling = copy_ceiling(idn, torch, x, y)
 
     pix_step = total_images * H * W
@@ -723,10 +790,12 @@ def main():
                 "timing": ("end-to-end op time (host gather, H2D, synchronous passes), not a "
                            "kernel duration" if args.op in END_TO_END else
                            "HIP events around the K launches on the launch stream"),
-                "kernel_ms_median_event_pairs": round(kern_ms[len(kern_ms) // 2], 5),
+                "kernel_ms_median_event_pairs": (round(kern_ms[len(kern_ms) // 2], 5)
+                                                 if kern_ms else None),
                 "algorithmic_bytes_per_launch": bpp * my_batch * H * W,
             },
-            "cpu_baseline": None if (args.no_cpu or world > 1) else cpu_baseline(args.op),
+            "cpu_baseline": (cpu_baseline(args.op)
+                             if args.full and not args.no_cpu and world == 1 else None),
         }
         if ceiling is not None:
             rec["copy_ceiling_GBps"] = ceiling["copy_ceiling_GBps"]

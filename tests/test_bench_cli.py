@@ -58,6 +58,42 @@ def test_single_gpu_default_is_one_rank():
     assert rec["n_gpus"] == 1 and rec["shards"] == [[0, 0, 256]]
 
 
+def test_plain_and_full_options_parse():
+    """--full and --dump-outputs exist, both off by default; --steps must be a real step count."""
+    sys.path.insert(0, str(ROOT))
+    import bench
+    import pytest
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    a = bench.parse_args(["--full", "--dump-outputs", "d", "--no-cpu"])
+    assert a.full is True and a.dump_outputs == "d" and a.no_cpu
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0"])
+
+
+def test_dump_snapshot_is_bounded_seeded_and_float():
+    """--dump-outputs arrays: float32 (float64 stays float64), whole when they fit their share of
+    the budget, else the same seeded sample of elements on every call."""
+    sys.path.insert(0, str(ROOT))
+    import bench
+    import numpy as np
+    import torch
+    small = torch.arange(24, dtype=torch.uint8).reshape(2, 3, 4)
+    f64 = np.linspace(0.0, 1.0, 5)
+    snap = bench.snapshot_outputs(torch, {"out": small, "scales": f64})
+    assert snap["out"].dtype == np.float32 and snap["out"].shape == (2, 3, 4)
+    assert np.array_equal(snap["out"], small.numpy().astype(np.float32))
+    assert snap["scales"].dtype == np.float64 and np.array_equal(snap["scales"], f64)
+    n = bench.DUMP_BUDGET // 4
+    big = (torch.arange(n + 1000, dtype=torch.int64) % 251).to(torch.uint8)
+    s1 = bench.snapshot_outputs(torch, {"out": big})["out"]
+    s2 = bench.snapshot_outputs(torch, {"out": big.clone()})["out"]
+    assert s1.dtype == np.float32 and s1.shape == (n,) and s1.nbytes <= 64 << 20
+    assert np.array_equal(s1, s2)
+    idx = np.sort(np.random.RandomState(20240607).randint(0, n + 1000, size=n, dtype=np.int64))
+    assert np.array_equal(s1, (idx % 251).astype(np.float32))
+
+
 def test_roofline_names_the_binding_roof():
     """The line carries the VALU roofline beside the HBM one where a committed PMC record gives
     the op's VALU lane-ops per pixel, and `bound` names the higher fraction."""

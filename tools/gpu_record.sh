@@ -21,8 +21,8 @@ tail -1 "$OUT/bench.jsonl"
 timeout -k 10 300 python bench.py --op detect_e2e_pipelined --no-cpu --no-copy --steps 400 --warmup 40 \
   >> "$OUT/bench.jsonl" 2> "$OUT/e2e.err" || exit 1
 tail -1 "$OUT/bench.jsonl"
-timeout -k 10 300 python bench.py > "$OUT/default.json" 2> "$OUT/default.err" || exit 1
+timeout -k 10 300 python bench.py --full > "$OUT/default.json" 2> "$OUT/default.err" || exit 1
 cat "$OUT/default.json"
 timeout -k 10 200 rocprofv3 --kernel-trace --stats -d "$(pwd)/$OUT/ks_default" -o k \
-  --output-format csv -- python3 bench.py --no-cpu > "$OUT/ks_default.log" 2>&1 || exit 1
+  --output-format csv -- python3 bench.py --full --no-cpu > "$OUT/ks_default.log" 2>&1 || exit 1
 echo ok

@@ -19,6 +19,6 @@ fi
 for v in $VALS; do
   if [ "$v" != default ]; then export "$NAME=$v"; fi
   timeout -s KILL 90 rocprofv3 --pmc $COUNTERS -d "$OUT/$v" -o pmc --output-format csv \
-    -- python3 bench.py --op "$OP" --no-cpu --steps 3 --warmup 1 > "$OUT/log_$v.txt" 2>&1 || exit 1
+    -- python3 bench.py --full --op "$OP" --no-cpu --steps 3 --warmup 1 > "$OUT/log_$v.txt" 2>&1 || exit 1
 done
 echo ok

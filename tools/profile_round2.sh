@@ -21,13 +21,13 @@ step() {  # step <secs> <name> <cmd...>
   if [ $rc -ne 0 ]; then echo "stopping"; exit $rc; fi
 }
 step 600 pytest_gpu python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout-method thread
-step 300 bench_default python bench.py
+step 300 bench_default python bench.py --full
 for op in $OPS; do
   timeout -k 10 200 python bench.py --op "$op" --no-cpu --no-copy --steps 50 --warmup 5 \
     >> "$OUT/bench_ops.jsonl" 2> "$OUT/bench_$op.err" || { echo "bench $op failed"; tail -20 "$OUT/bench_$op.err"; exit 1; }
   echo "bench $op ok"
 done
-step 300 prof_headline rocprofv3 --kernel-trace --stats -d "$ROOT/$OUT/prof_headline" -o k --output-format csv -- python3 bench.py --no-cpu
+step 300 prof_headline rocprofv3 --kernel-trace --stats -d "$ROOT/$OUT/prof_headline" -o k --output-format csv -- python3 bench.py --full --no-cpu
 step 120 pmc_fetch rocprofv3 --pmc FETCH_SIZE -d "$ROOT/$OUT/pmc_fetch" -o pmc --output-format csv -- python3 bench.py --no-cpu --no-copy --steps 5 --warmup 2 --settle-s 0
 step 120 pmc_write rocprofv3 --pmc WRITE_SIZE -d "$ROOT/$OUT/pmc_write" -o pmc --output-format csv -- python3 bench.py --no-cpu --no-copy --steps 5 --warmup 2 --settle-s 0
 echo done
