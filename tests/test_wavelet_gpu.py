@@ -548,8 +548,16 @@ def test_haar3_two_read_path(dev, monkeypatch, force_fb):
     min / max and nonzero counts bit for bit, sums to 1e-12 relative, sigma within the analytic
     bound (bitwise where the exact full-image selection ran: IDN_WAVELET_H3FB=1 forces it for every
     channel), outputs within 1e-6 and U8 flips only on rounding boundaries.  Without forcing, the
-    textured and noisy images must take the window path."""
+    textured and noisy images must take the window path.
+
+    At 96 x 160 the window kernel's sample is 3 level-1 rows x 80 columns = 240 values, below the
+    512 it needs to narrow the window, so every channel here keeps the full window (1, 0xFFFFFFFF)
+    and the unforced `fb == 0` says only that a median rank among the T != 0 lies inside the whole
+    image.  The integer model (tests/h3_model.py) states that window and the counters it implies,
+    asserted below; narrowed windows and fallbacks fired by the image itself are
+    tests/test_haar3_window_gpu.py's."""
     import torch
+    import h3_model
     from idn import _lib
     imgs = np.concatenate([_stat_images(96, 160),
                            np.stack([_clipped(96, 160, 3), _clipped(96, 160, 4)])])
@@ -575,7 +583,14 @@ def test_haar3_two_read_path(dev, monkeypatch, force_fb):
     else:
         # textured (2), noisy (3), uniform (4), clipped (7, 8): the window path
         assert np.all(sel[[2, 3, 4, 7, 8], :, 6] == 0), sel[:, :, 6]
-        rng = _key_to_f64(sb[:, 203:206].view(np.uint64)) - _key_to_f64(sb[:, 200:203].view(np.uint64))
+        for i in range(len(imgs)):  # no image here can narrow its window: the model's full one
+            M = h3_model.model(imgs[i])
+            for c in range(3):
+                ch = M.ch[c]
+                assert not ch.narrowed and (ch.lo, ch.hi) == (1, 0xFFFFFFFF)
+                assert tuple(int(v) for v in sel[i, c, :6]) == (
+                    1, 0xFFFFFFFF, ch.n_t, ch.n_lo, ch.n_t, M.n_r if c == 0 else 0), (i, c, sel[i, c])
+        rng =_key_to_f64(sb[:, 203:206].view(np.uint64)) - _key_to_f64(sb[:, 200:203].view(np.uint64))
         ok = np.abs(sa[:, med] - sb[:, med]) <= 2.1e-12 / np.maximum(rng, 1e-300)
         assert np.all(ok | (np.isnan(sa[:, med]) & np.isnan(sb[:, med])))
     live = _key_to_f64(sb[:, 203:206].view(np.uint64)) - _key_to_f64(sb[:, 200:203].view(np.uint64)) > 1e-6
