@@ -27,6 +27,8 @@
  *                against integer thresholds (|P - p| < 2^-16)
  *       poisson  Philox4x32-7, one block per 4 elements, 32-bit words inverted through the
  *                exact CDF of Poisson(img_as_float(v) * vals)
+ *     The host model tests/philox_model.py is the definition of these streams: the kernels are
+ *     tested against it draw for draw (tests/test_noise_streams_gpu.py).
  *     The tuning knobs of the kernels are compile-time constants: this library reads no
  *     environment variable.
  *   - Return IDN_OK (0) or a negative idn_status; idn_last_error() returns a thread-local
