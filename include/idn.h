@@ -82,8 +82,10 @@ typedef enum idn_wavelet {
  *   5  idn_noise_ycc_u8 and idn_wavelet_denoise_ycc added (no signature changed)
  *   6  cv2.imread's EXIF orientation: idn_jpeg_decode_u8 turns each image by it (flag
  *      IDN_JPEG_IGNORE_ORIENTATION keeps the decoded layout), idn_jpeg_info reports the turned
- *      size, idn_jpeg_orientation added */
-#define IDN_ABI_VERSION 6
+ *      size, idn_jpeg_orientation added
+ *   7  quality metrics: idn_metrics_workspace_size, idn_mse_u8 and idn_ssim_u8 added (no
+ *      signature changed) */
+#define IDN_ABI_VERSION 7
 int idn_abi_version(void);
 const char* idn_version(void);
 const char* idn_last_error(void);
@@ -295,6 +297,37 @@ int idn_gaussian_blur_f64(const double* src, double* dst, int n, int h, int w, i
                           void* stream);
 int idn_box_blur_f64(const double* src, double* dst, int n, int h, int w, int c, int ksize,
                      void* stream);
+
+/* ---- quality metrics (skimage 0.14.2 measure.compare_mse / compare_psnr / compare_ssim) ---- */
+
+/* Score a batch against another (a denoiser's output against the clean images) without leaving
+ * the device: one float64 per image pair.  a, b: u8 batches of the same shape, c in {1, 3}, each
+ * with its own row pitch.  Not a reference interface: the reference never scores its filters.
+ *
+ * idn_mse_u8: mse_out[i] = compare_mse(a[i], b[i]) = sum((a - b)^2) / (h*w*c).  The sum is
+ *   carried in integers and divided once, so the value is bit-equal to numpy's float64 mean.
+ *   compare_psnr is 10 log10(255^2 / mse) of it (idn.ops.psnr; +inf for equal images).
+ * idn_ssim_u8: ssim_out[i] = compare_ssim(a[i], b[i], win_size=win_size, multichannel=True)
+ *   (data_range 255, uniform window, sample covariance, K1 0.01, K2 0.03): per channel the mean
+ *   of S over the (h - win_size + 1) * (w - win_size + 1) windows that lie inside the image,
+ *   then the mean over channels.  win_size odd, 3..11, <= min(h, w).  The window moments are
+ *   exact integers, S and the sums are float64, and the sums run in a fixed order: a pair gives
+ *   the same bits on every call and in every batch, and a == b gives exactly 1.0.
+ *   ssim_ch_out (nullable): the n*c per-channel values.  mse_out (nullable): idn_mse_u8's
+ *   values, from the same pass over the bytes.
+ * workspace: idn_metrics_workspace_size(n, h, w, c, win_size) bytes, 8-byte aligned, for either
+ *   call (win_size outside 3..11: idn_mse_u8's need alone); 0 for a shape neither call accepts.
+ * IDN_EINVAL: null image or result pointer, row pitch < w*c, c not 1 or 3, win_size even or
+ *   outside 3..11 or above min(h, w).  IDN_EWORKSPACE: workspace missing or too small.
+ *   IDN_EUNSUPPORTED: idn_mse_u8 on images above 1 GiB. */
+size_t idn_metrics_workspace_size(int n, int h, int w, int c, int win_size);
+int idn_mse_u8(const uint8_t* a, const uint8_t* b, double* mse_out, int n, int h, int w, int c,
+               int64_t row_stride_a, int64_t row_stride_b, void* workspace,
+               size_t workspace_bytes, void* stream);
+int idn_ssim_u8(const uint8_t* a, const uint8_t* b, double* ssim_out, double* ssim_ch_out,
+                double* mse_out, int n, int h, int w, int c, int64_t row_stride_a,
+                int64_t row_stride_b, int win_size, void* workspace, size_t workspace_bytes,
+                void* stream);
 
 /* ---- shader / bloom noise types ---------------------------------------------------------- */
 
