@@ -19,6 +19,6 @@ int set_error(int status, const char* fmt, ...) {
 
 extern "C" int idn_abi_version(void) { return IDN_ABI_VERSION; }
 
-extern "C" const char* idn_version(void) { return "idn 0.5.0 gfx950"; }
+extern "C" const char* idn_version(void) { return "idn 0.6.0 gfx950"; }
 
 extern "C" const char* idn_last_error(void) { return idn::g_err; }

@@ -1,0 +1,280 @@
+// Non-local means on u8 images: OpenCV 3.4's 8-bit integer scheme (cv2.fastNlMeansDenoising;
+// fast_nlmeans_denoising_invoker.hpp with DistSquared, IT = int, WT = int), restated.  Not on the
+// reference's preprocessing path: it is the denoiser a cv2-flavoured bank is expected to have.
+// cv2 is not importable where this project is built, so parity with cv2 itself is unpinned (as
+// for the Lab tables of idn_quant_u8); the numpy host model tests/nlm_model.py is the contract and
+// the kernel matches it bit for bit.
+//
+//   fpm = INT_MAX / (s*s*255)     shift = ceil(log2(t*t))     mult = 2^shift / (t*t)
+//   wt[a] = rint(fpm * exp(-(a*mult) / (h*h*C))), 0 where below 0.001 * fpm   (host, float64)
+//   per pixel p, for each of the s*s offsets o, on the image extended by reflection (101):
+//     ssd = sum over the t x t template and the channels of (E[p+q] - E[p+o+q])^2
+//     w = wt[ssd >> shift];   wsum += w;   est[c] += w * E[p+o][c]
+//   out[c] = min(255, (est[c] + wsum / 2) / wsum)
+// est <= s*s*fpm*255 <= INT_MAX and wsum >= fpm (the zero offset weighs fpm), so u32 carries all.
+//
+// nlmeans_kernel<T, C>: a 256-thread workgroup owns NLM_OW(T) x 64 output pixels of one image.
+// The tile and a halo of T/2 + s/2 pixels is staged once in LDS, reflected while staging, one u32
+// per pixel (channel bytes packed, a fixed pitch of 84 so that row offsets are immediates), with
+// the nonzero prefix of the weight table and one zero entry behind it.  After the one barrier the
+// four waves never meet again: wave v owns output rows 16 v .. 16 v + 15.  A lane owns one
+// column.  Per offset it takes its 16 + T - 1 rows of squared differences
+//   D = |a|^2 + |b|^2 - 2 a.b   (v_dot4_u32_u8 on the packed pixels; |a|^2 does not depend on the
+//                                offset and stays in registers),
+// adds the T columns to its right through ds_bpermute (T = 7: D + D[+1], that + itself[+2], then
+// [+4] of the pair sum and D[+6]: four permutes), runs the box sum down the row sums, and for each
+// of its 16 rows looks the weight up in LDS (index clamped to n_weights, where the zero entry
+// stands for the table's zero tail) and runs C + 1 24-bit multiply-adds into the row's u32
+// accumulators.  Everything is unrolled over the rows, so the row sums and the 16 (C + 1)
+// accumulators are registers, and each stage runs over all rows before the next starts: its LDS
+// reads and permutes are in flight together (measured 100.5 -> 95.9 ms with the fixed pitch and
+// the zero entry, -> 91.3 ms with the stages, 256 x 600 x 1000 x 3).  The
+// 64 - (T - 1) lanes with a whole template to their right produce output.
+#include "idn_common.hpp"
+
+#include <limits.h>
+#include <math.h>
+
+namespace idn {
+
+constexpr int NLM_TH = 16;             // output rows per wave
+constexpr int NLM_ROWS = 4 * NLM_TH;   // output rows per workgroup
+constexpr int NLM_PITCH = 64 + 20;     // LDS tile pitch in pixels: 64 columns + the widest search
+constexpr int nlm_ow(int t) { return 64 - (t - 1); }  // output columns per workgroup
+constexpr int nlm_shift(int t) { return t == 3 ? 4 : (t == 5 ? 5 : 6); }
+
+__device__ __forceinline__ uint32_t nlm_dot(uint32_t a, uint32_t b, uint32_t acc) {
+  return __builtin_amdgcn_udot4(a, b, acc, false);
+}
+
+__device__ __forceinline__ uint32_t nlm_from_lane(uint32_t byte_addr, uint32_t v) {
+  return (uint32_t)__builtin_amdgcn_ds_bpermute((int)byte_addr, (int)v);
+}
+
+template <int T, int C>
+__global__ __launch_bounds__(256) void nlmeans_kernel(const uint8_t* __restrict__ src,
+                                                      uint8_t* __restrict__ dst, int h, int w,
+                                                      int64_t row_stride, int sr, int tiles_x,
+                                                      int tiles_y,
+                                                      const int32_t* __restrict__ weights,
+                                                      int n_weights) {
+  constexpr int TR = T / 2;
+  constexpr int OW = nlm_ow(T);
+  constexpr int SHIFT = nlm_shift(T);
+  constexpr int STEPS = NLM_TH + T - 1;
+  extern __shared__ uint32_t nlm_lds[];
+
+  const int b = TR + sr;
+  constexpr int twe = NLM_PITCH;
+  const int cols = 64 + 2 * sr;         // staged columns: OW + 2 b
+  const int the = NLM_ROWS + 2 * b;
+  uint32_t* tile = nlm_lds;
+  uint32_t* wt = nlm_lds + twe * the;
+
+  const int tid = threadIdx.x;
+  const int per_img = tiles_x * tiles_y;
+  const int img = blockIdx.x / per_img;
+  const int rem = blockIdx.x - img * per_img;
+  const int ty = rem / tiles_x;
+  const int tx = rem - ty * tiles_x;
+  const int gx0 = tx * OW, gy0 = ty * NLM_ROWS;
+  const uint8_t* simg = src + (int64_t)img * h * row_stride;
+
+  for (int i = tid; i < cols * the; i += 256) {
+    const int ey = i / cols, ex = i - ey * cols;
+    const uint8_t* p = simg + (int64_t)reflect101(gy0 - b + ey, h) * row_stride +
+                       (int64_t)reflect101(gx0 - b + ex, w) * C;
+    uint32_t v = p[0];
+    if (C == 3) v |= ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16);
+    tile[ey * twe + ex] = v;
+  }
+  for (int i = tid; i <= n_weights; i += 256) wt[i] = i < n_weights ? (uint32_t)weights[i] : 0u;
+  __syncthreads();
+
+  const int lane = tid & 63;
+  const int rowbase = (tid >> 6) * NLM_TH;
+  if (gy0 + rowbase >= h) return;  // a whole wave below the image (after the only barrier)
+
+  uint32_t wsum[NLM_TH], est[NLM_TH][C];
+#pragma unroll
+  for (int r = 0; r < NLM_TH; ++r) {
+    wsum[r] = 0;
+#pragma unroll
+    for (int ch = 0; ch < C; ++ch) est[r][ch] = 0;
+  }
+  // a: the template pixel of this lane's column of differences; ctr: the pixel a weight multiplies
+  const uint32_t* pa = tile + (sr + rowbase) * twe + sr + lane;
+  const uint32_t* pc = tile + (b + rowbase) * twe + b + min(lane, OW - 1);
+  const uint32_t l1 = ((lane + 1) & 63) * 4, l2 = ((lane + 2) & 63) * 4;
+  const uint32_t l4 = ((lane + 4) & 63) * 4, l6 = ((lane + 6) & 63) * 4;
+  const uint32_t nw = (uint32_t)n_weights;  // wt[nw] = 0 stands for the table's zero tail
+
+  for (int dy = -sr; dy <= sr; ++dy) {
+    for (int dx = -sr; dx <= sr; ++dx) {
+      const int off = dy * twe + dx;
+      // every stage runs over all rows before the next one starts, so that its LDS reads and
+      // lane permutes are in flight together instead of one round trip per row
+      uint32_t d[STEPS], d1[STEPS], hs[STEPS], ssd[NLM_TH], wgt[NLM_TH], px[NLM_TH];
+#pragma unroll
+      for (int j = 0; j < STEPS; ++j) {
+        const uint32_t a = pa[j * twe], q = pa[j * twe + off];
+        d[j] = nlm_dot(q, q, nlm_dot(a, a, 0)) - 2u * nlm_dot(a, q, 0);
+      }
+#pragma unroll
+      for (int j = 0; j < STEPS; ++j) d1[j] = d[j] + nlm_from_lane(l1, d[j]);  // columns +0 .. +1
+#pragma unroll
+      for (int j = 0; j < STEPS; ++j) {
+        if (T == 3) hs[j] = d1[j] + nlm_from_lane(l2, d[j]);
+        else hs[j] = d1[j] + nlm_from_lane(l2, d1[j]);                          // +0 .. +3
+      }
+      if (T == 5) {
+#pragma unroll
+        for (int j = 0; j < STEPS; ++j) hs[j] += nlm_from_lane(l4, d[j]);
+      }
+      if (T == 7) {
+#pragma unroll
+        for (int j = 0; j < STEPS; ++j) hs[j] += nlm_from_lane(l4, d1[j]) + nlm_from_lane(l6, d[j]);
+      }
+      uint32_t box = 0;
+#pragma unroll
+      for (int j = 0; j < STEPS; ++j) {
+        box += hs[j];
+        if (j >= T) box -= hs[j - T];
+        if (j >= T - 1) ssd[j - (T - 1)] = box;
+      }
+#pragma unroll
+      for (int r = 0; r < NLM_TH; ++r) {
+        wgt[r] = wt[min(ssd[r] >> SHIFT, nw)];
+        px[r] = pc[r * twe + off];
+      }
+#pragma unroll
+      for (int r = 0; r < NLM_TH; ++r) {
+        wsum[r] += wgt[r];
+        est[r][0] += __umul24(wgt[r], px[r] & 255u);
+        if (C == 3) {
+          est[r][1] += __umul24(wgt[r], (px[r] >> 8) & 255u);
+          est[r][2] += __umul24(wgt[r], px[r] >> 16);
+        }
+      }
+    }
+  }
+
+  const int gx = gx0 + lane;
+  if (lane >= OW || gx >= w) return;
+  uint8_t* dimg = dst + (int64_t)img * h * row_stride + (int64_t)gx * C;
+#pragma unroll
+  for (int r = 0; r < NLM_TH; ++r) {
+    const int gy = gy0 + rowbase + r;
+    if (gy < h) {
+      uint8_t* o = dimg + (int64_t)gy * row_stride;
+#pragma unroll
+      for (int ch = 0; ch < C; ++ch)
+        o[ch] = (uint8_t)min(255u, (est[r][ch] + wsum[r] / 2u) / wsum[r]);
+    }
+  }
+}
+
+static bool nlm_sizes_ok(int t, int s) {
+  return (t & 1) && t >= 3 && t <= 7 && (s & 1) && s >= 5 && s <= 21;
+}
+
+// A launch gets 64 KB of LDS without asking; a longer weight table raises the kernel's limit first
+// (up to the CU's 160 KB; one workgroup per CU above 80 KB).  Not a stream operation.
+template <int T, int C>
+static hipError_t launch_nlm_c(unsigned grid, size_t lds, hipStream_t st, const uint8_t* src,
+                               uint8_t* dst, int h, int w, int64_t row_stride, int sr,
+                               int tiles_x, int tiles_y, const int32_t* weights, int n_weights) {
+  if (lds > 64 * 1024) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&nlmeans_kernel<T, C>),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL((nlmeans_kernel<T, C>), dim3(grid), dim3(256), lds, st, src, dst, h, w,
+                     row_stride, sr, tiles_x, tiles_y, weights, n_weights);
+  return hipGetLastError();
+}
+
+template <int T>
+static hipError_t launch_nlm(int c, unsigned grid, size_t lds, hipStream_t st, const uint8_t* src,
+                             uint8_t* dst, int h, int w, int64_t row_stride, int sr, int tiles_x,
+                             int tiles_y, const int32_t* weights, int n_weights) {
+  return c == 3 ? launch_nlm_c<T, 3>(grid, lds, st, src, dst, h, w, row_stride, sr, tiles_x,
+                                     tiles_y, weights, n_weights)
+                : launch_nlm_c<T, 1>(grid, lds, st, src, dst, h, w, row_stride, sr, tiles_x,
+                                     tiles_y, weights, n_weights);
+}
+
+}  // namespace idn
+
+extern "C" int idn_nlmeans_weights(double h, int c, int template_size, int search_size,
+                                   int32_t* wt_out, int cap, int* n_weights, int* shift,
+                                   int* fixed_point_mult) {
+  using namespace idn;
+  IDN_CHECK_ARG(n_weights && shift && fixed_point_mult && (wt_out || cap == 0),
+                "idn_nlmeans_weights: null pointer");
+  IDN_CHECK_ARG(cap >= 0, "idn_nlmeans_weights: negative cap %d", cap);
+  IDN_CHECK_ARG(h > 0.0 && h < INFINITY, "idn_nlmeans_weights: h must be positive and finite "
+                "(got %g)", h);
+  IDN_CHECK_ARG(c == 1 || c == 3, "idn_nlmeans_weights: channels must be 1 or 3 (got %d)", c);
+  IDN_CHECK_ARG(nlm_sizes_ok(template_size, search_size),
+                "idn_nlmeans_weights: template_size must be odd in 3..7 and search_size odd in "
+                "5..21 (got %d, %d)", template_size, search_size);
+  const int tt = template_size * template_size;
+  const int fpm = INT_MAX / (search_size * search_size * 255);
+  const int sh = nlm_shift(template_size);
+  const double mult = (double)(1 << sh) / (double)tt;
+  const int len = (int)(255.0 * 255.0 * c / mult + 1);
+  const double den = h * h * c;
+  const double thr = 0.001 * fpm;
+  int n = 0;
+  for (; n < len; ++n) {  // exp falls monotonically: the first entry below the threshold ends it
+    const double wgt = nearbyint(fpm * exp(-(n * mult) / den));
+    if (wgt < thr) break;
+    if (n < cap) wt_out[n] = (int32_t)wgt;
+  }
+  *n_weights = n;
+  *shift = sh;
+  *fixed_point_mult = fpm;
+  return IDN_OK;
+}
+
+extern "C" int idn_nlmeans_u8(const uint8_t* src, uint8_t* dst, int n, int h, int w, int c,
+                              int64_t row_stride, int template_size, int search_size,
+                              const int32_t* weights_dev, int n_weights, void* stream) {
+  using namespace idn;
+  IDN_CHECK_ARG(src && dst && weights_dev, "idn_nlmeans_u8: null pointer");
+  IDN_CHECK_ARG(src != dst, "idn_nlmeans_u8: in-place filtering is not supported (src == dst)");
+  IDN_CHECK_ARG(n >= 0 && h > 0 && w > 0, "idn_nlmeans_u8: bad shape n=%d h=%d w=%d", n, h, w);
+  IDN_CHECK_ARG(c == 1 || c == 3, "idn_nlmeans_u8: channels must be 1 or 3 (got %d)", c);
+  IDN_CHECK_ARG(row_stride >= (int64_t)w * c, "idn_nlmeans_u8: row_stride %lld < w*c",
+                (long long)row_stride);
+  IDN_CHECK_ARG(nlm_sizes_ok(template_size, search_size),
+                "idn_nlmeans_u8: template_size must be odd in 3..7 and search_size odd in 5..21 "
+                "(got %d, %d)", template_size, search_size);
+  const int sr = search_size / 2, b = template_size / 2 + sr;
+  IDN_CHECK_ARG(h > b && w > b, "idn_nlmeans_u8: image %d x %d smaller than the %d pixels the "
+                "template and search windows need", h, w, b + 1);
+  IDN_CHECK_ARG(n_weights >= 1, "idn_nlmeans_u8: n_weights must be positive (got %d)", n_weights);
+  if (n_weights > IDN_NLMEANS_MAX_WEIGHTS)
+    return set_error(IDN_EUNSUPPORTED, "idn_nlmeans_u8: a weight table of %d entries exceeds "
+                     "IDN_NLMEANS_MAX_WEIGHTS (%d): h is too large", n_weights,
+                     IDN_NLMEANS_MAX_WEIGHTS);
+  if (n == 0) return IDN_OK;
+  const int tiles_x = (w + nlm_ow(template_size) - 1) / nlm_ow(template_size);
+  const int tiles_y = (h + NLM_ROWS - 1) / NLM_ROWS;
+  if ((int64_t)n * tiles_x * tiles_y > (int64_t)INT_MAX)
+    return set_error(IDN_EUNSUPPORTED, "idn_nlmeans_u8: batch too large for one launch");
+  const unsigned grid = (unsigned)(n * tiles_x * tiles_y);
+  const size_t lds = ((size_t)NLM_PITCH * (NLM_ROWS + 2 * b) + (size_t)n_weights + 1) * 4;
+  const hipStream_t st = as_stream(stream);
+  hipError_t e;
+  switch (template_size) {
+    case 3: e = launch_nlm<3>(c, grid, lds, st, src, dst, h, w, row_stride, sr, tiles_x, tiles_y, weights_dev, n_weights); break;
+    case 5: e = launch_nlm<5>(c, grid, lds, st, src, dst, h, w, row_stride, sr, tiles_x, tiles_y, weights_dev, n_weights); break;
+    default: e = launch_nlm<7>(c, grid, lds, st, src, dst, h, w, row_stride, sr, tiles_x, tiles_y, weights_dev, n_weights); break;
+  }
+  if (e != hipSuccess)
+    return set_error(IDN_EHIP, "idn_nlmeans_u8: launch failed (%zu bytes of LDS): %s", lds,
+                     hipGetErrorString(e));
+  return IDN_OK;
+}

@@ -15,7 +15,7 @@ import threading
 from pathlib import Path
 
 LIB_PATH = Path(__file__).resolve().parent / "libidn_hip.so"
-ABI_VERSION = 7  # IDN_ABI_VERSION of include/idn.h that SIGNATURES binds
+ABI_VERSION = 8  # IDN_ABI_VERSION of include/idn.h that SIGNATURES binds
 VARIANTS = {"tuning": Path(__file__).resolve().parent / "libidn_hip_tuning.so"}
 
 _c_u8p = ctypes.c_void_p
@@ -79,6 +79,9 @@ SIGNATURES = {
     "idn_wavelet_stats_offset": (_c_size, [_c_int, _c_int, _c_int, _c_int, _c_int]),
     "idn_gaussian_blur_f64": (_c_int, [_c_vp, _c_vp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_vp]),
     "idn_box_blur_f64": (_c_int, [_c_vp, _c_vp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_vp]),
+    "idn_nlmeans_weights": (_c_int, [_c_dbl, _c_int, _c_int, _c_int, _c_vp, _c_int, _c_vp, _c_vp, _c_vp]),
+    "idn_nlmeans_u8": (_c_int, [_c_u8p, _c_u8p, _c_int, _c_int, _c_int, _c_int, _c_i64, _c_int, _c_int,
+                                _c_vp, _c_int, _c_vp]),
     "idn_metrics_workspace_size": (_c_size, [_c_int, _c_int, _c_int, _c_int, _c_int]),
     "idn_mse_u8": (_c_int, [_c_u8p, _c_u8p, _c_f64p, _c_int, _c_int, _c_int, _c_int, _c_i64, _c_i64,
                             _c_vp, _c_size, _c_vp]),

@@ -13,12 +13,14 @@ the OpenCV / scikit-image calls the reference makes on its preprocessing path:
   denoise_wavelet(x, wavelet, levels)     skimage.restoration.denoise_wavelet (0.14.2 wrapper)
   blob(x, ...)                            lib/utils/blob.py prep_im_for_blob + im_list_to_blob
   mse / psnr / ssim(x, y)                 skimage.measure.compare_mse / _psnr / _ssim (0.14.2)
+  nl_means(x, h, t, s)                    cv2.fastNlMeansDenoising(x, None, h, t, s) (3.4, 8-bit)
 
 There is no CPU path: a CPU tensor raises, a missing library raises.
 """
 from __future__ import annotations
 
 import ctypes
+import numbers
 from typing import Optional, Tuple
 
 import numpy as np
@@ -655,6 +657,98 @@ def denoise_wavelet(x: torch.Tensor, wavelet: str = "bior1.5", levels: Optional[
     if out == "f32":
         return _finish(y32, sq)
     return _finish(y8, sq), _finish(y32, sq)
+
+
+# ---- non-local means -----------------------------------------------------------------------------
+
+NLMEANS_MAX_WEIGHTS = 24576  # IDN_NLMEANS_MAX_WEIGHTS of include/idn.h
+
+_NLM_CACHE: dict = {}
+
+
+def nl_means_weights(h: float, channels: int, template_window: int = 7, search_window: int = 21):
+    """The nonzero prefix of OpenCV's fixed-point weight table as an int32 numpy array, with the
+    shift and the fixed-point multiplier (idn_nlmeans_weights; host only, no GPU needed)."""
+    lib = _lib.load()
+    n, shift, fpm = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+    args = (float(h), int(channels), int(template_window), int(search_window))
+    refs = (ctypes.byref(n), ctypes.byref(shift), ctypes.byref(fpm))
+    _lib.check(lib.idn_nlmeans_weights(*args, None, 0, *refs), "idn_nlmeans_weights")
+    wt = np.empty(n.value, dtype=np.int32)
+    _lib.check(lib.idn_nlmeans_weights(*args, wt.ctypes.data, wt.size, *refs), "idn_nlmeans_weights")
+    return wt, shift.value, fpm.value
+
+
+def _row_pitch(t: torch.Tensor):
+    """row pitch in bytes of a (N,H,W,C) uint8 tensor whose rows are compact or padded (images
+    h*pitch apart), or None for any other layout"""
+    n, h, w, c = t.shape
+    sn, sh, sw, sc = t.stride()
+    if sc == 1 and sw == c and sh >= w * c and (n == 1 or sn == h * sh):
+        return sh
+    return None
+
+
+def nl_means(x: torch.Tensor, h: float = 3.0, template_window: int = 7, search_window: int = 21,
+             out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """cv2.fastNlMeansDenoising(x, None, h, template_window, search_window) in OpenCV 3.4's 8-bit
+    integer scheme, per image; 1 or 3 channels (3 channels are denoised jointly, as cv2 does for a
+    3-channel input: this is not fastNlMeansDenoisingColored).  Bit-equal to the numpy model
+    tests/nlm_model.py.  h must be of the order of the noise's standard deviation on the 0..255
+    scale: far below it every patch but the pixel's own gets weight 0 and the input comes back.
+    x may be contiguous or have padded rows; out, if given, must then share x's layout."""
+    if not isinstance(x, torch.Tensor):
+        raise TypeError(f"nl_means: expected a torch.Tensor, got {type(x).__name__}")
+    if x.dtype != torch.uint8:
+        raise TypeError(f"nl_means: expected uint8 images, got {x.dtype}")
+    if x.dim() not in (3, 4):
+        raise ValueError(f"nl_means: expected (H,W,C) or (N,H,W,C), got shape {tuple(x.shape)}")
+    if x.shape[-1] not in (1, 3):
+        raise ValueError(f"nl_means: 1 or 3 channels supported, got {x.shape[-1]}")
+    t, s = template_window, search_window
+    if t not in (3, 5, 7):
+        raise ValueError(f"nl_means: template_window must be odd and in 3..7, got {t!r}")
+    if s not in range(5, 22, 2):
+        raise ValueError(f"nl_means: search_window must be odd and in 5..21, got {s!r}")
+    if not (isinstance(h, numbers.Real) and 0 < h < float("inf")):
+        raise ValueError(f"nl_means: h must be positive and finite, got {h!r}")
+    need = t // 2 + s // 2 + 1
+    if min(x.shape[-3], x.shape[-2]) < need:
+        raise ValueError(f"nl_means: image {x.shape[-3]} x {x.shape[-2]} smaller than the {need} "
+                         "pixels the template and search windows need")
+    t, s = int(t), int(s)
+    xb, sq = _as_batch(x, "nl_means")
+    n, hh, w, c = xb.shape
+    if out is not None:
+        if out.dtype != torch.uint8 or out.shape != x.shape or out.device != x.device:
+            raise ValueError("nl_means: out must be a uint8 tensor shaped like x on x's device")
+        y = out.unsqueeze(0) if sq else out
+        pitch = _row_pitch(y)
+        if pitch is None:
+            raise ValueError("nl_means: out must have compact or padded rows")
+        if _row_pitch(xb) != pitch:
+            if pitch != w * c:
+                raise ValueError("nl_means: a padded out needs x in the same layout")
+            xb = xb.contiguous()
+        if y.data_ptr() == xb.data_ptr():
+            raise ValueError("nl_means: in-place filtering is not supported (out is x)")
+    else:
+        pitch = w * c
+        xb = xb.contiguous()
+        y = torch.empty_like(xb)
+    key = (str(xb.device), float(h), c, t, s)
+    wt = _NLM_CACHE.get(key)
+    if wt is None:
+        host, _, _ = nl_means_weights(h, c, t, s)
+        if host.size > NLMEANS_MAX_WEIGHTS:
+            raise _lib.IdnError(f"nl_means: unsupported: h = {h} gives a weight table of {host.size} "
+                                f"entries, above NLMEANS_MAX_WEIGHTS ({NLMEANS_MAX_WEIGHTS})")
+        wt = torch.from_numpy(host).to(xb.device)
+        _NLM_CACHE[key] = wt
+    rc = _lib.load().idn_nlmeans_u8(xb.data_ptr(), y.data_ptr(), n, hh, w, c, pitch, t, s,
+                                    wt.data_ptr(), wt.numel(), _stream())
+    _lib.check(rc, "idn_nlmeans_u8")
+    return out if out is not None else _finish(y, sq)
 
 
 # ---- quality metrics ---------------------------------------------------------------------------

@@ -84,8 +84,9 @@ typedef enum idn_wavelet {
  *      IDN_JPEG_IGNORE_ORIENTATION keeps the decoded layout), idn_jpeg_info reports the turned
  *      size, idn_jpeg_orientation added
  *   7  quality metrics: idn_metrics_workspace_size, idn_mse_u8 and idn_ssim_u8 added (no
- *      signature changed) */
-#define IDN_ABI_VERSION 7
+ *      signature changed)
+ *   8  non-local means: idn_nlmeans_weights and idn_nlmeans_u8 added (no signature changed) */
+#define IDN_ABI_VERSION 8
 int idn_abi_version(void);
 const char* idn_version(void);
 const char* idn_last_error(void);
@@ -297,6 +298,42 @@ int idn_gaussian_blur_f64(const double* src, double* dst, int n, int h, int w, i
                           void* stream);
 int idn_box_blur_f64(const double* src, double* dst, int n, int h, int w, int c, int ksize,
                      void* stream);
+
+/* ---- non-local means (cv2.fastNlMeansDenoising, OpenCV 3.4's 8-bit integer scheme) ---------- */
+
+/* Not a reference interface: the denoiser a cv2-flavoured bank is expected to have.  The scheme
+ * (fast_nlmeans_denoising_invoker.hpp, DistSquared, IT = int, WT = int) is pure integer
+ * arithmetic; tests/nlm_model.py restates it in numpy and the kernel matches that model bit for
+ * bit.  cv2 is not importable where this project is built, so parity with cv2 itself is unpinned.
+ * With t = template_size (odd, 3..7), s = search_size (odd, 5..21), b = t/2 + s/2:
+ *   fpm = INT_MAX / (s*s*255), shift = ceil(log2(t*t)), mult = 2^shift / (t*t)
+ *   wt[a] = rint(fpm * exp(-(a*mult) / (h*h*c))), 0 where below 0.001 * fpm
+ *   per pixel p and each of the s*s offsets o, on the image reflected (BORDER_REFLECT_101) by b:
+ *     ssd = sum over the t x t template and the channels of (E[p+q] - E[p+o+q])^2
+ *     w = wt[ssd >> shift];  wsum += w;  est[ch] += w * E[p+o][ch]
+ *   dst[ch] = min(255, (est[ch] + wsum/2) / wsum)
+ * h must be of the order of the noise's standard deviation on the 0..255 scale.
+ *
+ * idn_nlmeans_weights (host only, no HIP call): the table is a nonzero prefix followed by zeros;
+ *   writes the first min(cap, prefix length) entries to wt_out and reports the full prefix length
+ *   in *n_weights (a cap that is too small is not an error: call again with a larger buffer),
+ *   shift and fpm.  IDN_EINVAL: null pointer (wt_out may be null when cap is 0), cap < 0, h not
+ *   positive and finite, c not 1 or 3, sizes even or out of range.
+ * idn_nlmeans_u8: weights_dev is that prefix on the device (n_weights entries; built once per
+ *   (h, c, t, s) and kept by the caller); shift and fpm follow from the sizes.  Stream-ordered and
+ *   capture-safe: no allocation, copy or synchronisation inside.  src and dst share row_stride.
+ *   IDN_EINVAL: null pointer, src == dst, row_stride < w*c, c not 1 or 3, sizes even or out of
+ *   range, min(h, w) < b + 1, n_weights < 1.  IDN_EUNSUPPORTED: n_weights above
+ *   IDN_NLMEANS_MAX_WEIGHTS (the prefix lives in LDS next to the 30 KB tile; 24576 is h ~ 39 at
+ *   c = 3, t = 7.  Up to 8800 entries, h ~ 23, the launch stays within the 64 KB every launch
+ *   gets; above, the kernel's LDS limit is raised first, and above 12900 entries, h ~ 28, only
+ *   one workgroup fits a CU instead of two).  Every argument check runs before any HIP call. */
+#define IDN_NLMEANS_MAX_WEIGHTS 24576
+int idn_nlmeans_weights(double h, int c, int template_size, int search_size, int32_t* wt_out,
+                        int cap, int* n_weights, int* shift, int* fixed_point_mult);
+int idn_nlmeans_u8(const uint8_t* src, uint8_t* dst, int n, int h, int w, int c,
+                   int64_t row_stride, int template_size, int search_size,
+                   const int32_t* weights_dev, int n_weights, void* stream);
 
 /* ---- quality metrics (skimage 0.14.2 measure.compare_mse / compare_psnr / compare_ssim) ---- */
 
