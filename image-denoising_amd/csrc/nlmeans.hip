@@ -30,7 +30,22 @@
 // reads and permutes are in flight together (measured 100.5 -> 95.9 ms with the fixed pitch and
 // the zero entry, -> 91.3 ms with the stages, 256 x 600 x 1000 x 3).  The
 // 64 - (T - 1) lanes with a whole template to their right produce output.
+//
+// cv2.fastNlMeansDenoisingColored (idn_nlmeans_colored_u8) is two launches of the same kernel on a
+// BGR source, with the 8-bit linear Lab conversions (COLOR_LBGR2Lab / COLOR_Lab2LBGR; lab_cvt.hpp)
+// folded into its staging and output stages, so no Lab image ever lies in memory:
+//   NLM_LAB_L  (C = 1): staging converts each staged BGR pixel and keeps L; the output stage writes
+//              L' to a compact 1 byte/pixel plane (the caller's workspace).
+//   NLM_LAB_AB (C = 2, a | b << 16, the other two bytes zero, so the dot products stay exact):
+//              staging keeps (a, b); the output stage reads its pixel's L' from the plane,
+//              converts (L', a', b') back and writes BGR.  b must sit in byte 2, not byte 1:
+//              packed as a | b << 8 the two clamped shifts become one v_ashr_pk_u8_i32, whose
+//              16-bit result hipcc (ROCm 7) stores as a dword without clearing the destination's
+//              upper half, and byte 2 of the staged pixel is garbage.
+// The cbrt table (and LabToYF_b for the way back) is staged in LDS behind the weights, before the
+// tile: these two modes have one barrier more.  NLM_PLAIN is the kernel described above.
 #include "idn_common.hpp"
+#include "lab_cvt.hpp"
 
 #include <limits.h>
 #include <math.h>
@@ -51,13 +66,19 @@ __device__ __forceinline__ uint32_t nlm_from_lane(uint32_t byte_addr, uint32_t v
   return (uint32_t)__builtin_amdgcn_ds_bpermute((int)byte_addr, (int)v);
 }
 
-template <int T, int C>
+enum { NLM_PLAIN = 0, NLM_LAB_L = 1, NLM_LAB_AB = 2 };
+constexpr int NLM_CBRT_BYTES = 3072 * 2, NLM_YF_BYTES = 512 * 2;  // LAB_CBRT_B, LAB_YF_B in LDS
+
+// lplane: NLM_LAB_AB only, the L' plane the NLM_LAB_L launch wrote (n * h * w bytes)
+template <int T, int C, int MODE = NLM_PLAIN>
 __global__ __launch_bounds__(256) void nlmeans_kernel(const uint8_t* __restrict__ src,
                                                       uint8_t* __restrict__ dst, int h, int w,
                                                       int64_t row_stride, int sr, int tiles_x,
                                                       int tiles_y,
                                                       const int32_t* __restrict__ weights,
-                                                      int n_weights) {
+                                                      int n_weights,
+                                                      const uint8_t* __restrict__ lplane) {
+  static_assert(MODE == NLM_PLAIN ? (C == 1 || C == 3) : C == MODE, "mode and channel count");
   constexpr int TR = T / 2;
   constexpr int OW = nlm_ow(T);
   constexpr int SHIFT = nlm_shift(T);
@@ -80,13 +101,31 @@ __global__ __launch_bounds__(256) void nlmeans_kernel(const uint8_t* __restrict_
   const int gx0 = tx * OW, gy0 = ty * NLM_ROWS;
   const uint8_t* simg = src + (int64_t)img * h * row_stride;
 
-  for (int i = tid; i < cols * the; i += 256) {
-    const int ey = i / cols, ex = i - ey * cols;
-    const uint8_t* p = simg + (int64_t)reflect101(gy0 - b + ey, h) * row_stride +
-                       (int64_t)reflect101(gx0 - b + ex, w) * C;
-    uint32_t v = p[0];
-    if (C == 3) v |= ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16);
-    tile[ey * twe + ex] = v;
+  // Lab modes: the cbrt table, then LabToYF_b, behind the n_weights + 1 weights
+  uint16_t* ct = reinterpret_cast<uint16_t*>(wt + n_weights + 1);
+  const uint16_t* yf = ct + 3072;
+  if constexpr (MODE == NLM_PLAIN) {
+    for (int i = tid; i < cols * the; i += 256) {
+      const int ey = i / cols, ex = i - ey * cols;
+      const uint8_t* p = simg + (int64_t)reflect101(gy0 - b + ey, h) * row_stride +
+                         (int64_t)reflect101(gx0 - b + ex, w) * C;
+      uint32_t v = p[0];
+      if (C == 3) v |= ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16);
+      tile[ey * twe + ex] = v;
+    }
+  } else {
+    for (int i = tid; i < 3072; i += 256) ct[i] = LAB_CBRT_B[i];
+    if constexpr (MODE == NLM_LAB_AB)
+      for (int i = tid; i < 512; i += 256) ct[3072 + i] = LAB_YF_B[i];
+    __syncthreads();
+    for (int i = tid; i < cols * the; i += 256) {
+      const int ey = i / cols, ex = i - ey * cols;
+      const uint8_t* p = simg + (int64_t)reflect101(gy0 - b + ey, h) * row_stride +
+                         (int64_t)reflect101(gx0 - b + ex, w) * 3;
+      const uint32_t lab = lab_from_bgr<true>(p[0], p[1], p[2], nullptr, ct);
+      tile[ey * twe + ex] = MODE == NLM_LAB_L ? (lab & 255u)
+                                              : (((lab >> 8) & 255u) | (lab & 0xFF0000u));
+    }
   }
   for (int i = tid; i <= n_weights; i += 256) wt[i] = i < n_weights ? (uint32_t)weights[i] : 0u;
   __syncthreads();
@@ -155,21 +194,45 @@ __global__ __launch_bounds__(256) void nlmeans_kernel(const uint8_t* __restrict_
           est[r][1] += __umul24(wgt[r], (px[r] >> 8) & 255u);
           est[r][2] += __umul24(wgt[r], px[r] >> 16);
         }
+        if (C == 2) est[r][1] += __umul24(wgt[r], px[r] >> 16);
       }
     }
   }
 
   const int gx = gx0 + lane;
   if (lane >= OW || gx >= w) return;
-  uint8_t* dimg = dst + (int64_t)img * h * row_stride + (int64_t)gx * C;
+  if constexpr (MODE == NLM_PLAIN) {
+    uint8_t* dimg = dst + (int64_t)img * h * row_stride + (int64_t)gx * C;
 #pragma unroll
-  for (int r = 0; r < NLM_TH; ++r) {
-    const int gy = gy0 + rowbase + r;
-    if (gy < h) {
-      uint8_t* o = dimg + (int64_t)gy * row_stride;
+    for (int r = 0; r < NLM_TH; ++r) {
+      const int gy = gy0 + rowbase + r;
+      if (gy < h) {
+        uint8_t* o = dimg + (int64_t)gy * row_stride;
 #pragma unroll
-      for (int ch = 0; ch < C; ++ch)
-        o[ch] = (uint8_t)min(255u, (est[r][ch] + wsum[r] / 2u) / wsum[r]);
+        for (int ch = 0; ch < C; ++ch)
+          o[ch] = (uint8_t)min(255u, (est[r][ch] + wsum[r] / 2u) / wsum[r]);
+      }
+    }
+  } else {
+    const int64_t pimg = (int64_t)img * h * w + gx;  // this column in the compact L' plane
+    uint8_t* dimg = dst + (int64_t)img * h * row_stride + (int64_t)gx * 3;
+#pragma unroll
+    for (int r = 0; r < NLM_TH; ++r) {
+      const int gy = gy0 + rowbase + r;
+      if (gy < h) {
+        uint32_t v[C];
+#pragma unroll
+        for (int ch = 0; ch < C; ++ch) v[ch] = min(255u, (est[r][ch] + wsum[r] / 2u) / wsum[r]);
+        if constexpr (MODE == NLM_LAB_L) {
+          dst[pimg + (int64_t)gy * w] = (uint8_t)v[0];
+        } else {
+          const uint32_t bgr = bgr_from_lab<true>(lplane[pimg + (int64_t)gy * w], v[0], v[1], yf);
+          uint8_t* o = dimg + (int64_t)gy * row_stride;
+          o[0] = (uint8_t)bgr;
+          o[1] = (uint8_t)(bgr >> 8);
+          o[2] = (uint8_t)(bgr >> 16);
+        }
+      }
     }
   }
 }
@@ -180,17 +243,19 @@ static bool nlm_sizes_ok(int t, int s) {
 
 // A launch gets 64 KB of LDS without asking; a longer weight table raises the kernel's limit first
 // (up to the CU's 160 KB; one workgroup per CU above 80 KB).  Not a stream operation.
-template <int T, int C>
+template <int T, int C, int MODE = NLM_PLAIN>
 static hipError_t launch_nlm_c(unsigned grid, size_t lds, hipStream_t st, const uint8_t* src,
                                uint8_t* dst, int h, int w, int64_t row_stride, int sr,
-                               int tiles_x, int tiles_y, const int32_t* weights, int n_weights) {
+                               int tiles_x, int tiles_y, const int32_t* weights, int n_weights,
+                               const uint8_t* lplane = nullptr) {
   if (lds > 64 * 1024) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&nlmeans_kernel<T, C>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    const hipError_t e =
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&nlmeans_kernel<T, C, MODE>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
   }
-  hipLaunchKernelGGL((nlmeans_kernel<T, C>), dim3(grid), dim3(256), lds, st, src, dst, h, w,
-                     row_stride, sr, tiles_x, tiles_y, weights, n_weights);
+  hipLaunchKernelGGL((nlmeans_kernel<T, C, MODE>), dim3(grid), dim3(256), lds, st, src, dst, h, w,
+                     row_stride, sr, tiles_x, tiles_y, weights, n_weights, lplane);
   return hipGetLastError();
 }
 
@@ -202,6 +267,39 @@ static hipError_t launch_nlm(int c, unsigned grid, size_t lds, hipStream_t st, c
                                      tiles_y, weights, n_weights)
                 : launch_nlm_c<T, 1>(grid, lds, st, src, dst, h, w, row_stride, sr, tiles_x,
                                      tiles_y, weights, n_weights);
+}
+
+// the L launch into the plane, then the ab launch that reads it: ordered on the stream
+template <int T>
+static hipError_t launch_nlm_colored(unsigned grid, size_t lds_l, size_t lds_ab, hipStream_t st,
+                                     const uint8_t* src, uint8_t* dst, int h, int w,
+                                     int64_t row_stride, int sr, int tiles_x, int tiles_y,
+                                     const int32_t* wt_l, int n_l, const int32_t* wt_ab, int n_ab,
+                                     uint8_t* lplane) {
+  const hipError_t e = launch_nlm_c<T, 1, NLM_LAB_L>(grid, lds_l, st, src, lplane, h, w, row_stride,
+                                                     sr, tiles_x, tiles_y, wt_l, n_l);
+  if (e != hipSuccess) return e;
+  return launch_nlm_c<T, 2, NLM_LAB_AB>(grid, lds_ab, st, src, dst, h, w, row_stride, sr, tiles_x,
+                                        tiles_y, wt_ab, n_ab, lplane);
+}
+
+// the nonzero prefix of the weight table of (h, c, t, s): the first min(cap, length) entries go
+// to wt_out; returns the length
+static int nlm_fill_weights(double h, int c, int template_size, int search_size, int32_t* wt_out,
+                            int cap) {
+  const int tt = template_size * template_size;
+  const int fpm = INT_MAX / (search_size * search_size * 255);
+  const double mult = (double)(1 << nlm_shift(template_size)) / (double)tt;
+  const int len = (int)(255.0 * 255.0 * c / mult + 1);
+  const double den = h * h * c;
+  const double thr = 0.001 * fpm;
+  int n = 0;
+  for (; n < len; ++n) {  // exp falls monotonically: the first entry below the threshold ends it
+    const double wgt = nearbyint(fpm * exp(-(n * mult) / den));
+    if (wgt < thr) break;
+    if (n < cap) wt_out[n] = (int32_t)wgt;
+  }
+  return n;
 }
 
 }  // namespace idn
@@ -219,22 +317,9 @@ extern "C" int idn_nlmeans_weights(double h, int c, int template_size, int searc
   IDN_CHECK_ARG(nlm_sizes_ok(template_size, search_size),
                 "idn_nlmeans_weights: template_size must be odd in 3..7 and search_size odd in "
                 "5..21 (got %d, %d)", template_size, search_size);
-  const int tt = template_size * template_size;
-  const int fpm = INT_MAX / (search_size * search_size * 255);
-  const int sh = nlm_shift(template_size);
-  const double mult = (double)(1 << sh) / (double)tt;
-  const int len = (int)(255.0 * 255.0 * c / mult + 1);
-  const double den = h * h * c;
-  const double thr = 0.001 * fpm;
-  int n = 0;
-  for (; n < len; ++n) {  // exp falls monotonically: the first entry below the threshold ends it
-    const double wgt = nearbyint(fpm * exp(-(n * mult) / den));
-    if (wgt < thr) break;
-    if (n < cap) wt_out[n] = (int32_t)wgt;
-  }
-  *n_weights = n;
-  *shift = sh;
-  *fixed_point_mult = fpm;
+  *n_weights = nlm_fill_weights(h, c, template_size, search_size, wt_out, cap);
+  *shift = nlm_shift(template_size);
+  *fixed_point_mult = INT_MAX / (search_size * search_size * 255);
   return IDN_OK;
 }
 
@@ -276,5 +361,82 @@ extern "C" int idn_nlmeans_u8(const uint8_t* src, uint8_t* dst, int n, int h, in
   if (e != hipSuccess)
     return set_error(IDN_EHIP, "idn_nlmeans_u8: launch failed (%zu bytes of LDS): %s", lds,
                      hipGetErrorString(e));
+  return IDN_OK;
+}
+
+extern "C" int idn_nlmeans_colored_weights(double h, double h_color, int template_size,
+                                           int search_size, int32_t* wt_l, int cap_l, int* n_l,
+                                           int32_t* wt_ab, int cap_ab, int* n_ab, int* shift,
+                                           int* fixed_point_mult) {
+  using namespace idn;
+  IDN_CHECK_ARG(n_l && n_ab && shift && fixed_point_mult && (wt_l || cap_l == 0) &&
+                (wt_ab || cap_ab == 0), "idn_nlmeans_colored_weights: null pointer");
+  IDN_CHECK_ARG(cap_l >= 0 && cap_ab >= 0, "idn_nlmeans_colored_weights: negative cap %d / %d",
+                cap_l, cap_ab);
+  IDN_CHECK_ARG(h > 0.0 && h < INFINITY, "idn_nlmeans_colored_weights: h must be positive and "
+                "finite (got %g)", h);
+  IDN_CHECK_ARG(h_color > 0.0 && h_color < INFINITY, "idn_nlmeans_colored_weights: h_color must "
+                "be positive and finite (got %g)", h_color);
+  IDN_CHECK_ARG(nlm_sizes_ok(template_size, search_size),
+                "idn_nlmeans_colored_weights: template_size must be odd in 3..7 and search_size "
+                "odd in 5..21 (got %d, %d)", template_size, search_size);
+  *n_l = nlm_fill_weights(h, 1, template_size, search_size, wt_l, cap_l);
+  *n_ab = nlm_fill_weights(h_color, 2, template_size, search_size, wt_ab, cap_ab);
+  *shift = nlm_shift(template_size);
+  *fixed_point_mult = INT_MAX / (search_size * search_size * 255);
+  return IDN_OK;
+}
+
+extern "C" size_t idn_nlmeans_colored_workspace_size(int n, int h, int w) {
+  if (n <= 0 || h <= 0 || w <= 0) return 0;
+  return ((size_t)n * h * w + 255) & ~(size_t)255;
+}
+
+extern "C" int idn_nlmeans_colored_u8(const uint8_t* src, uint8_t* dst, int n, int h, int w,
+                                      int64_t row_stride, int template_size, int search_size,
+                                      const int32_t* wt_l_dev, int n_l, const int32_t* wt_ab_dev,
+                                      int n_ab, void* workspace, size_t ws_bytes, void* stream) {
+  using namespace idn;
+  const char* const name = "idn_nlmeans_colored_u8";
+  IDN_CHECK_ARG(src && dst && wt_l_dev && wt_ab_dev, "%s: null pointer", name);
+  IDN_CHECK_ARG(src != dst, "%s: in-place filtering is not supported (src == dst)", name);
+  IDN_CHECK_ARG(n >= 0 && h > 0 && w > 0, "%s: bad shape n=%d h=%d w=%d", name, n, h, w);
+  IDN_CHECK_ARG(row_stride >= (int64_t)w * 3, "%s: row_stride %lld < w*3", name,
+                (long long)row_stride);
+  IDN_CHECK_ARG(nlm_sizes_ok(template_size, search_size),
+                "%s: template_size must be odd in 3..7 and search_size odd in 5..21 (got %d, %d)",
+                name, template_size, search_size);
+  const int sr = search_size / 2, b = template_size / 2 + sr;
+  IDN_CHECK_ARG(h > b && w > b, "%s: image %d x %d smaller than the %d pixels the template and "
+                "search windows need", name, h, w, b + 1);
+  IDN_CHECK_ARG(n_l >= 1 && n_ab >= 1, "%s: n_weights must be positive (got %d, %d)", name, n_l,
+                n_ab);
+  if (n_l > IDN_NLMEANS_MAX_WEIGHTS || n_ab > IDN_NLMEANS_MAX_WEIGHTS)
+    return set_error(IDN_EUNSUPPORTED, "%s: a weight table of %d / %d entries exceeds "
+                     "IDN_NLMEANS_MAX_WEIGHTS (%d): h or h_color is too large", name, n_l, n_ab,
+                     IDN_NLMEANS_MAX_WEIGHTS);
+  const size_t need = idn_nlmeans_colored_workspace_size(n, h, w);
+  IDN_CHECK_ARG(need == 0 || (workspace && ws_bytes >= need), "%s: needs %zu workspace bytes "
+                "(got %zu)", name, need, workspace ? ws_bytes : (size_t)0);
+  if (n == 0) return IDN_OK;
+  const int tiles_x = (w + nlm_ow(template_size) - 1) / nlm_ow(template_size);
+  const int tiles_y = (h + NLM_ROWS - 1) / NLM_ROWS;
+  if ((int64_t)n * tiles_x * tiles_y > (int64_t)INT_MAX)
+    return set_error(IDN_EUNSUPPORTED, "%s: batch too large for one launch", name);
+  const unsigned grid = (unsigned)(n * tiles_x * tiles_y);
+  const size_t tile = (size_t)NLM_PITCH * (NLM_ROWS + 2 * b);
+  const size_t lds_l = (tile + (size_t)n_l + 1) * 4 + NLM_CBRT_BYTES;
+  const size_t lds_ab = (tile + (size_t)n_ab + 1) * 4 + NLM_CBRT_BYTES + NLM_YF_BYTES;
+  const hipStream_t st = as_stream(stream);
+  uint8_t* plane = static_cast<uint8_t*>(workspace);
+  hipError_t e;
+  switch (template_size) {
+    case 3: e = launch_nlm_colored<3>(grid, lds_l, lds_ab, st, src, dst, h, w, row_stride, sr, tiles_x, tiles_y, wt_l_dev, n_l, wt_ab_dev, n_ab, plane); break;
+    case 5: e = launch_nlm_colored<5>(grid, lds_l, lds_ab, st, src, dst, h, w, row_stride, sr, tiles_x, tiles_y, wt_l_dev, n_l, wt_ab_dev, n_ab, plane); break;
+    default: e = launch_nlm_colored<7>(grid, lds_l, lds_ab, st, src, dst, h, w, row_stride, sr, tiles_x, tiles_y, wt_l_dev, n_l, wt_ab_dev, n_ab, plane); break;
+  }
+  if (e != hipSuccess)
+    return set_error(IDN_EHIP, "%s: launch failed (%zu / %zu bytes of LDS): %s", name, lds_l,
+                     lds_ab, hipGetErrorString(e));
   return IDN_OK;
 }

@@ -15,7 +15,7 @@ import threading
 from pathlib import Path
 
 LIB_PATH = Path(__file__).resolve().parent / "libidn_hip.so"
-ABI_VERSION = 8  # IDN_ABI_VERSION of include/idn.h that SIGNATURES binds
+ABI_VERSION = 9  # IDN_ABI_VERSION of include/idn.h that SIGNATURES binds
 VARIANTS = {"tuning": Path(__file__).resolve().parent / "libidn_hip_tuning.so"}
 
 _c_u8p = ctypes.c_void_p
@@ -68,6 +68,8 @@ SIGNATURES = {
     "idn_quant_workspace_size": (_c_size, [_c_int, _c_int]),
     "idn_bgr2lab_u8": (_c_int, [_c_u8p, _c_u8p, _c_int, _c_int, _c_int, _c_i64, _c_vp]),
     "idn_lab2bgr_u8": (_c_int, [_c_u8p, _c_u8p, _c_int, _c_int, _c_int, _c_i64, _c_vp]),
+    "idn_lbgr2lab_u8": (_c_int, [_c_u8p, _c_u8p, _c_int, _c_int, _c_int, _c_i64, _c_vp]),
+    "idn_lab2lbgr_u8": (_c_int, [_c_u8p, _c_u8p, _c_int, _c_int, _c_int, _c_i64, _c_vp]),
     "idn_gaussian_blob_f32": (_c_int, [_c_u8p, _c_vp, _c_int, _c_int, _c_int, _c_int, _c_i64, _c_int,
                                        ctypes.POINTER(ctypes.c_double), _c_vp]),
     "idn_copy_u8": (_c_int, [_c_u8p, _c_u8p, _c_i64, _c_int, _c_vp]),
@@ -82,6 +84,12 @@ SIGNATURES = {
     "idn_nlmeans_weights": (_c_int, [_c_dbl, _c_int, _c_int, _c_int, _c_vp, _c_int, _c_vp, _c_vp, _c_vp]),
     "idn_nlmeans_u8": (_c_int, [_c_u8p, _c_u8p, _c_int, _c_int, _c_int, _c_int, _c_i64, _c_int, _c_int,
                                 _c_vp, _c_int, _c_vp]),
+    "idn_nlmeans_colored_weights": (_c_int, [_c_dbl, _c_dbl, _c_int, _c_int, _c_vp, _c_int, _c_vp,
+                                             _c_vp, _c_int, _c_vp, _c_vp, _c_vp]),
+    "idn_nlmeans_colored_workspace_size": (_c_size, [_c_int, _c_int, _c_int]),
+    "idn_nlmeans_colored_u8": (_c_int, [_c_u8p, _c_u8p, _c_int, _c_int, _c_int, _c_i64, _c_int,
+                                        _c_int, _c_vp, _c_int, _c_vp, _c_int, _c_vp, _c_size,
+                                        _c_vp]),
     "idn_metrics_workspace_size": (_c_size, [_c_int, _c_int, _c_int, _c_int, _c_int]),
     "idn_mse_u8": (_c_int, [_c_u8p, _c_u8p, _c_f64p, _c_int, _c_int, _c_int, _c_int, _c_i64, _c_i64,
                             _c_vp, _c_size, _c_vp]),

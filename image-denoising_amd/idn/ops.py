@@ -14,6 +14,7 @@ the OpenCV / scikit-image calls the reference makes on its preprocessing path:
   blob(x, ...)                            lib/utils/blob.py prep_im_for_blob + im_list_to_blob
   mse / psnr / ssim(x, y)                 skimage.measure.compare_mse / _psnr / _ssim (0.14.2)
   nl_means(x, h, t, s)                    cv2.fastNlMeansDenoising(x, None, h, t, s) (3.4, 8-bit)
+  nl_means_colored(x, h, h_color, t, s)   cv2.fastNlMeansDenoisingColored(x, None, h, h_color, t, s)
 
 There is no CPU path: a CPU tensor raises, a missing library raises.
 """
@@ -543,14 +544,18 @@ def quantize(x: torch.Tensor, k: int, *, seed: int = 0, offset: int = 0, image_i
     return res[0] if len(res) == 1 else tuple(res)
 
 
-def cvt_color_lab(x: torch.Tensor, to_lab: bool = True) -> torch.Tensor:
-    """cv2.cvtColor(x, COLOR_BGR2LAB) (to_lab) or (x, COLOR_LAB2BGR) on 8-bit 3-channel images."""
+def cvt_color_lab(x: torch.Tensor, to_lab: bool = True, linear: bool = False) -> torch.Tensor:
+    """cv2.cvtColor(x, COLOR_BGR2LAB) (to_lab) or (x, COLOR_LAB2BGR) on 8-bit 3-channel images;
+    linear=True: COLOR_LBGR2Lab / COLOR_Lab2LBGR (no sRGB gamma; nl_means_colored's conversions)."""
     xb, sq = _u8_batch(x, "cvt_color_lab")
     n, h, w, c = xb.shape
     if c != 3:
         raise ValueError("cvt_color_lab: needs 3 channels")
     y = torch.empty_like(xb)
-    fn = "idn_bgr2lab_u8" if to_lab else "idn_lab2bgr_u8"
+    if linear:
+        fn = "idn_lbgr2lab_u8" if to_lab else "idn_lab2lbgr_u8"
+    else:
+        fn = "idn_bgr2lab_u8" if to_lab else "idn_lab2bgr_u8"
     _lib.check(getattr(_lib.load(), fn)(xb.data_ptr(), y.data_ptr(), n, h, w, w * 3, _stream()), fn)
     return _finish(y, sq)
 
@@ -689,65 +694,138 @@ def _row_pitch(t: torch.Tensor):
     return None
 
 
-def nl_means(x: torch.Tensor, h: float = 3.0, template_window: int = 7, search_window: int = 21,
-             out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """cv2.fastNlMeansDenoising(x, None, h, template_window, search_window) in OpenCV 3.4's 8-bit
-    integer scheme, per image; 1 or 3 channels (3 channels are denoised jointly, as cv2 does for a
-    3-channel input: this is not fastNlMeansDenoisingColored).  Bit-equal to the numpy model
-    tests/nlm_model.py.  h must be of the order of the noise's standard deviation on the 0..255
-    scale: far below it every patch but the pixel's own gets weight 0 and the input comes back.
-    x may be contiguous or have padded rows; out, if given, must then share x's layout."""
+def _nlm_check(name: str, x, channels, t, s, strengths) -> None:
+    """argument errors of the non-local means wrappers, raised before the device is looked at"""
     if not isinstance(x, torch.Tensor):
-        raise TypeError(f"nl_means: expected a torch.Tensor, got {type(x).__name__}")
+        raise TypeError(f"{name}: expected a torch.Tensor, got {type(x).__name__}")
     if x.dtype != torch.uint8:
-        raise TypeError(f"nl_means: expected uint8 images, got {x.dtype}")
+        raise TypeError(f"{name}: expected uint8 images, got {x.dtype}")
     if x.dim() not in (3, 4):
-        raise ValueError(f"nl_means: expected (H,W,C) or (N,H,W,C), got shape {tuple(x.shape)}")
-    if x.shape[-1] not in (1, 3):
-        raise ValueError(f"nl_means: 1 or 3 channels supported, got {x.shape[-1]}")
-    t, s = template_window, search_window
+        raise ValueError(f"{name}: expected (H,W,C) or (N,H,W,C), got shape {tuple(x.shape)}")
+    if x.shape[-1] not in channels:
+        raise ValueError(f"{name}: {' or '.join(map(str, channels))} channels supported, "
+                         f"got {x.shape[-1]}")
     if t not in (3, 5, 7):
-        raise ValueError(f"nl_means: template_window must be odd and in 3..7, got {t!r}")
+        raise ValueError(f"{name}: template_window must be odd and in 3..7, got {t!r}")
     if s not in range(5, 22, 2):
-        raise ValueError(f"nl_means: search_window must be odd and in 5..21, got {s!r}")
-    if not (isinstance(h, numbers.Real) and 0 < h < float("inf")):
-        raise ValueError(f"nl_means: h must be positive and finite, got {h!r}")
+        raise ValueError(f"{name}: search_window must be odd and in 5..21, got {s!r}")
+    for what, h in strengths:
+        if not (isinstance(h, numbers.Real) and 0 < h < float("inf")):
+            raise ValueError(f"{name}: {what} must be positive and finite, got {h!r}")
     need = t // 2 + s // 2 + 1
     if min(x.shape[-3], x.shape[-2]) < need:
-        raise ValueError(f"nl_means: image {x.shape[-3]} x {x.shape[-2]} smaller than the {need} "
+        raise ValueError(f"{name}: image {x.shape[-3]} x {x.shape[-2]} smaller than the {need} "
                          "pixels the template and search windows need")
-    t, s = int(t), int(s)
-    xb, sq = _as_batch(x, "nl_means")
+
+
+def _nlm_layout(name: str, x: torch.Tensor, out: Optional[torch.Tensor]):
+    """(source batch, destination batch, their common row pitch, squeeze) of x and out"""
+    xb, sq = _as_batch(x, name)
     n, hh, w, c = xb.shape
     if out is not None:
         if out.dtype != torch.uint8 or out.shape != x.shape or out.device != x.device:
-            raise ValueError("nl_means: out must be a uint8 tensor shaped like x on x's device")
+            raise ValueError(f"{name}: out must be a uint8 tensor shaped like x on x's device")
         y = out.unsqueeze(0) if sq else out
         pitch = _row_pitch(y)
         if pitch is None:
-            raise ValueError("nl_means: out must have compact or padded rows")
+            raise ValueError(f"{name}: out must have compact or padded rows")
         if _row_pitch(xb) != pitch:
             if pitch != w * c:
-                raise ValueError("nl_means: a padded out needs x in the same layout")
+                raise ValueError(f"{name}: a padded out needs x in the same layout")
             xb = xb.contiguous()
         if y.data_ptr() == xb.data_ptr():
-            raise ValueError("nl_means: in-place filtering is not supported (out is x)")
+            raise ValueError(f"{name}: in-place filtering is not supported (out is x)")
     else:
         pitch = w * c
         xb = xb.contiguous()
         y = torch.empty_like(xb)
-    key = (str(xb.device), float(h), c, t, s)
+    return xb, y, pitch, sq
+
+
+def _nlm_table(name: str, device, what: str, h, c: int, t: int, s: int) -> torch.Tensor:
+    """the weight table of (h, c, t, s) on the device, built once per device and key"""
+    key = (str(device), float(h), c, t, s)
     wt = _NLM_CACHE.get(key)
     if wt is None:
-        host, _, _ = nl_means_weights(h, c, t, s)
+        if c == 2:
+            host = nl_means_colored_weights(1.0, h, t, s)[1]
+        else:
+            host, _, _ = nl_means_weights(h, c, t, s)
         if host.size > NLMEANS_MAX_WEIGHTS:
-            raise _lib.IdnError(f"nl_means: unsupported: h = {h} gives a weight table of {host.size} "
-                                f"entries, above NLMEANS_MAX_WEIGHTS ({NLMEANS_MAX_WEIGHTS})")
-        wt = torch.from_numpy(host).to(xb.device)
+            raise _lib.IdnError(f"{name}: unsupported: {what} = {h} gives a weight table of "
+                                f"{host.size} entries, above NLMEANS_MAX_WEIGHTS "
+                                f"({NLMEANS_MAX_WEIGHTS})")
+        wt = torch.from_numpy(host).to(device)
         _NLM_CACHE[key] = wt
+    return wt
+
+
+def nl_means(x: torch.Tensor, h: float = 3.0, template_window: int = 7, search_window: int = 21,
+             out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """cv2.fastNlMeansDenoising(x, None, h, template_window, search_window) in OpenCV 3.4's 8-bit
+    integer scheme, per image; 1 or 3 channels (3 channels are denoised jointly, as cv2 does for a
+    3-channel input: this is not fastNlMeansDenoisingColored, which is nl_means_colored).  Bit-equal
+    to the numpy model tests/nlm_model.py.  h must be of the order of the noise's standard
+    deviation on the 0..255 scale: far below it every patch but the pixel's own gets weight 0 and
+    the input comes back.  x may be contiguous or have padded rows; out, if given, must then share
+    x's layout."""
+    t, s = template_window, search_window
+    _nlm_check("nl_means", x, (1, 3), t, s, (("h", h),))
+    t, s = int(t), int(s)
+    xb, y, pitch, sq = _nlm_layout("nl_means", x, out)
+    n, hh, w, c = xb.shape
+    wt = _nlm_table("nl_means", xb.device, "h", h, c, t, s)
     rc = _lib.load().idn_nlmeans_u8(xb.data_ptr(), y.data_ptr(), n, hh, w, c, pitch, t, s,
                                     wt.data_ptr(), wt.numel(), _stream())
     _lib.check(rc, "idn_nlmeans_u8")
+    return out if out is not None else _finish(y, sq)
+
+
+def nl_means_colored_weights(h: float, h_color: float, template_window: int = 7,
+                             search_window: int = 21):
+    """The two weight tables of nl_means_colored as int32 numpy arrays, (h, 1 channel) for L and
+    (h_color, 2 channels) for (a, b), with the shift and the fixed-point multiplier
+    (idn_nlmeans_colored_weights; host only, no GPU needed)."""
+    lib = _lib.load()
+    nl, nab, shift, fpm = (ctypes.c_int(0) for _ in range(4))
+    args = (float(h), float(h_color), int(template_window), int(search_window))
+    tail = (ctypes.byref(shift), ctypes.byref(fpm))
+    rc = lib.idn_nlmeans_colored_weights(*args, None, 0, ctypes.byref(nl), None, 0,
+                                         ctypes.byref(nab), *tail)
+    _lib.check(rc, "idn_nlmeans_colored_weights")
+    wl = np.empty(nl.value, dtype=np.int32)
+    wab = np.empty(nab.value, dtype=np.int32)
+    rc = lib.idn_nlmeans_colored_weights(*args, wl.ctypes.data, wl.size, ctypes.byref(nl),
+                                         wab.ctypes.data, wab.size, ctypes.byref(nab), *tail)
+    _lib.check(rc, "idn_nlmeans_colored_weights")
+    return wl, wab, shift.value, fpm.value
+
+
+def nl_means_colored(x: torch.Tensor, h: float = 3.0, h_color: float = 3.0,
+                     template_window: int = 7, search_window: int = 21,
+                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """cv2.fastNlMeansDenoisingColored(x, None, h, h_color, template_window, search_window) on
+    uint8 BGR images, per image: to 8-bit Lab with OpenCV's linear conversion (COLOR_LBGR2Lab),
+    nl_means on L with h and on (a, b) jointly with h_color, and back (COLOR_Lab2LBGR).  Bit-equal
+    to the numpy model tests/nlm_colored_model.py.  The 8-bit Lab round trip is not the identity:
+    with strengths too small to change anything the result is still up to (4, 2, 5) away from x in
+    (B, G, R).  h and h_color are on the 0..255 scale of the Lab bytes and of the order of the
+    noise there.  x may be contiguous or have padded rows; out, if given, must then share x's
+    layout."""
+    t, s = template_window, search_window
+    _nlm_check("nl_means_colored", x, (3,), t, s, (("h", h), ("h_color", h_color)))
+    t, s = int(t), int(s)
+    xb, y, pitch, sq = _nlm_layout("nl_means_colored", x, out)
+    n, hh, w, _ = xb.shape
+    wl = _nlm_table("nl_means_colored", xb.device, "h", h, 1, t, s)
+    wab = _nlm_table("nl_means_colored", xb.device, "h_color", h_color, 2, t, s)
+    lib = _lib.load()
+    nbytes = lib.idn_nlmeans_colored_workspace_size(n, hh, w)
+    ws = _workspace(nbytes, xb.device)
+    rc = lib.idn_nlmeans_colored_u8(xb.data_ptr(), y.data_ptr(), n, hh, w, pitch, t, s,
+                                    wl.data_ptr(), wl.numel(), wab.data_ptr(), wab.numel(),
+                                    ws.data_ptr(), nbytes, _stream())
+    _lib.check(rc, "idn_nlmeans_colored_u8")
     return out if out is not None else _finish(y, sq)
 
 

@@ -85,8 +85,11 @@ typedef enum idn_wavelet {
  *      size, idn_jpeg_orientation added
  *   7  quality metrics: idn_metrics_workspace_size, idn_mse_u8 and idn_ssim_u8 added (no
  *      signature changed)
- *   8  non-local means: idn_nlmeans_weights and idn_nlmeans_u8 added (no signature changed) */
-#define IDN_ABI_VERSION 8
+ *   8  non-local means: idn_nlmeans_weights and idn_nlmeans_u8 added (no signature changed)
+ *   9  colour non-local means: idn_lbgr2lab_u8, idn_lab2lbgr_u8, idn_nlmeans_colored_weights,
+ *      idn_nlmeans_colored_workspace_size and idn_nlmeans_colored_u8 added (no signature
+ *      changed) */
+#define IDN_ABI_VERSION 9
 int idn_abi_version(void);
 const char* idn_version(void);
 const char* idn_last_error(void);
@@ -244,6 +247,14 @@ int idn_bgr2lab_u8(const uint8_t* src, uint8_t* dst, int n, int h, int w, int64_
                    void* stream);
 int idn_lab2bgr_u8(const uint8_t* src, uint8_t* dst, int n, int h, int w, int64_t row_stride,
                    void* stream);
+/* cv2.cvtColor(img, COLOR_LBGR2Lab) / (lab, COLOR_Lab2LBGR): the same integer paths with OpenCV's
+ * linear gamma tables (linearGammaTab_b[i] = i << 3 in, linearInvGammaTab_b[v] = (255 * v) >> 12
+ * out) in place of the sRGB ones; what fastNlMeansDenoisingColored converts with.  At 8 bits the
+ * round trip is not the identity (it moves B, G, R by up to 4, 2, 5).  Parity vs cv2 unpinned. */
+int idn_lbgr2lab_u8(const uint8_t* src, uint8_t* dst, int n, int h, int w, int64_t row_stride,
+                    void* stream);
+int idn_lab2lbgr_u8(const uint8_t* src, uint8_t* dst, int n, int h, int w, int64_t row_stride,
+                    void* stream);
 
 /* ---- fused steps (one pass over HBM instead of two) ------------------------------------------ */
 
@@ -334,6 +345,41 @@ int idn_nlmeans_weights(double h, int c, int template_size, int search_size, int
 int idn_nlmeans_u8(const uint8_t* src, uint8_t* dst, int n, int h, int w, int c,
                    int64_t row_stride, int template_size, int search_size,
                    const int32_t* weights_dev, int n_weights, void* stream);
+
+/* cv2.fastNlMeansDenoisingColored(src, None, h, hColor, t, s) on 8-bit BGR images (c = 3), OpenCV
+ * 3.4's definition restated:
+ *   lab = cvtColor(src, COLOR_LBGR2Lab)                        (idn_lbgr2lab_u8)
+ *   L'  = fastNlMeansDenoising(lab[..., 0:1], h, t, s)         (the scheme above with c = 1)
+ *   ab' = fastNlMeansDenoising(lab[..., 1:3], hColor, t, s)    (c = 2: a and b denoised jointly)
+ *   dst = cvtColor(merge(L', ab'), COLOR_Lab2LBGR)             (idn_lab2lbgr_u8)
+ * tests/nlm_colored_model.py restates it in numpy and the kernels match that model bit for bit;
+ * parity with cv2 itself is unpinned (cv2 is not importable where this project is built; the two
+ * linear gamma tables are recalled from initLabTabs()).  Because the 8-bit Lab round trip is not
+ * the identity, a constant image comes back as lab2lbgr(lbgr2lab(x)), not as x.
+ *
+ * idn_nlmeans_colored_weights (host only): both tables at once, as two idn_nlmeans_weights calls
+ *   with (h, c = 1) and (h_color, c = 2) would give them if c = 2 were accepted there; caps and
+ *   lengths per table, a short cap is not an error.  IDN_EINVAL: null pointer (a table pointer may
+ *   be null when its cap is 0), a negative cap, h or h_color not positive and finite, bad sizes.
+ * idn_nlmeans_colored_workspace_size: bytes of the L' plane (at least n*h*w); 0 for a bad shape.
+ * idn_nlmeans_colored_u8: two launches ordered on the stream, no Lab image in memory: the first
+ *   converts while staging, denoises L and writes L' to the workspace (compact, w bytes per row);
+ *   the second converts while staging, denoises (a, b), reads L', converts back and writes BGR.
+ *   Stream-ordered and capture-safe: no allocation, copy or synchronisation inside.  src and dst
+ *   share row_stride; src == dst is rejected (the second launch still reads src).
+ *   IDN_EINVAL: null pointer, src == dst, row_stride < 3w, bad shape or sizes, min(h, w) < b + 1,
+ *   a table length below 1, workspace missing or below idn_nlmeans_colored_workspace_size.
+ *   IDN_EUNSUPPORTED: either table above IDN_NLMEANS_MAX_WEIGHTS (at t = 7, s = 21: h up to 68,
+ *   h_color up to 48).  n == 0 returns IDN_OK without a launch.  Every argument check runs before
+ *   any HIP call. */
+int idn_nlmeans_colored_weights(double h, double h_color, int template_size, int search_size,
+                                int32_t* wt_l, int cap_l, int* n_l, int32_t* wt_ab, int cap_ab,
+                                int* n_ab, int* shift, int* fixed_point_mult);
+size_t idn_nlmeans_colored_workspace_size(int n, int h, int w);
+int idn_nlmeans_colored_u8(const uint8_t* src, uint8_t* dst, int n, int h, int w,
+                           int64_t row_stride, int template_size, int search_size,
+                           const int32_t* wt_l_dev, int n_l, const int32_t* wt_ab_dev, int n_ab,
+                           void* workspace, size_t ws_bytes, void* stream);
 
 /* ---- quality metrics (skimage 0.14.2 measure.compare_mse / compare_psnr / compare_ssim) ---- */
 
