@@ -15,7 +15,7 @@ import threading
 from pathlib import Path
 
 LIB_PATH = Path(__file__).resolve().parent / "libidn_hip.so"
-ABI_VERSION = 9  # IDN_ABI_VERSION of include/idn.h that SIGNATURES binds
+ABI_VERSION = 10  # IDN_ABI_VERSION of include/idn.h that SIGNATURES binds
 VARIANTS = {"tuning": Path(__file__).resolve().parent / "libidn_hip_tuning.so"}
 
 _c_u8p = ctypes.c_void_p
@@ -90,6 +90,9 @@ SIGNATURES = {
     "idn_nlmeans_colored_u8": (_c_int, [_c_u8p, _c_u8p, _c_int, _c_int, _c_int, _c_i64, _c_int,
                                         _c_int, _c_vp, _c_int, _c_vp, _c_int, _c_vp, _c_size,
                                         _c_vp]),
+    "idn_tv_chambolle_workspace_size": (_c_size, [_c_int, _c_int, _c_int, _c_int]),
+    "idn_tv_chambolle_u8": (_c_int, [_c_u8p, _c_u8p, _c_vp, _c_vp, _c_int, _c_int, _c_int, _c_int,
+                                     _c_i64, _c_dbl, _c_dbl, _c_int, _c_vp, _c_size, _c_vp]),
     "idn_metrics_workspace_size": (_c_size, [_c_int, _c_int, _c_int, _c_int, _c_int]),
     "idn_mse_u8": (_c_int, [_c_u8p, _c_u8p, _c_f64p, _c_int, _c_int, _c_int, _c_int, _c_i64, _c_i64,
                             _c_vp, _c_size, _c_vp]),

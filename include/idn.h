@@ -88,8 +88,10 @@ typedef enum idn_wavelet {
  *   8  non-local means: idn_nlmeans_weights and idn_nlmeans_u8 added (no signature changed)
  *   9  colour non-local means: idn_lbgr2lab_u8, idn_lab2lbgr_u8, idn_nlmeans_colored_weights,
  *      idn_nlmeans_colored_workspace_size and idn_nlmeans_colored_u8 added (no signature
- *      changed) */
-#define IDN_ABI_VERSION 9
+ *      changed)
+ *  10  total-variation denoising: idn_tv_chambolle_workspace_size and idn_tv_chambolle_u8 added
+ *      (no signature changed) */
+#define IDN_ABI_VERSION 10
 int idn_abi_version(void);
 const char* idn_version(void);
 const char* idn_last_error(void);
@@ -380,6 +382,41 @@ int idn_nlmeans_colored_u8(const uint8_t* src, uint8_t* dst, int n, int h, int w
                            int64_t row_stride, int template_size, int search_size,
                            const int32_t* wt_l_dev, int n_l, const int32_t* wt_ab_dev, int n_ab,
                            void* workspace, size_t ws_bytes, void* stream);
+
+/* ---- total-variation denoising (skimage 0.14.2 restoration.denoise_tv_chambolle) ------------- */
+
+/* Not a reference interface: the edge-preserving denoiser of the module the reference takes its
+ * wavelet denoiser from.  denoise_tv_chambolle(x, weight, eps, n_iter_max, multichannel=True) on
+ * u8 images: every channel of every image is denoised on its own as im = x[..., ch] / 255 by
+ * Chambolle's projection iteration on the dual field (p0, p1), and stops on its own when the
+ * energy E of an iteration differs from the previous one's by less than eps * E(iteration 0), or
+ * after n_iter_max iterations.  tests/tv_model.py restates the algorithm in numpy float64 and is
+ * the definition; skimage is not importable where this project is built, so parity with skimage
+ * itself is unpinned.  The kernels keep the duals in fp32 and add the energies in fp64 in a fixed
+ * order: a channel's result, its iteration count included, is the same bits on every call and in
+ * every batch, and lies within 1e-5 of the model.
+ *   dst_f32 (nullable): out, float32, dense n*h*w*c, not clipped
+ *   dst_u8  (nullable): clip(rint(255 * out), 0, 255), row pitch row_stride as src
+ *   iters   (nullable): n*c int32, the iteration each (image, channel) stopped at: the index of the
+ *     iteration that met the rule (out is then the image formed from the duals before that
+ *     iteration's update), or n_iter_max.  A constant channel never meets the rule; eps = 0 gives
+ *     a fixed count.
+ * One launch per iteration plus two at the end; the stopping rule is evaluated on the device and
+ * the workgroups of a finished (image, channel) exit at once.  Stream-ordered and capture-safe: no
+ * allocation, copy or synchronisation inside.  src is read by every launch and must not be dst_u8.
+ * workspace: idn_tv_chambolle_workspace_size(n, h, w, c) bytes (0 for a shape the call does not
+ *   accept), 8-byte aligned, contents irrelevant on entry: two buffers of fp32 dual pairs, 16 bytes
+ *   per pixel and channel (48 bytes per pixel at c = 3: 7.4 GB for 256 images of 600 x 1000 x 3),
+ *   plus 32 bytes per 256 x 64 pixel tile and 64 bytes per (image, channel).
+ * IDN_EINVAL: null src, both destinations null, dst_u8 == src, h or w < 1, c not 1 or 3,
+ *   row_stride < w*c, weight not positive and finite, eps negative or not finite, n_iter_max
+ *   outside 1..IDN_TV_MAX_ITER.  IDN_EWORKSPACE: workspace missing or too small.  n == 0 returns
+ *   IDN_OK without a launch.  Every argument check runs before any HIP call. */
+#define IDN_TV_MAX_ITER 1000
+size_t idn_tv_chambolle_workspace_size(int n, int h, int w, int c);
+int idn_tv_chambolle_u8(const uint8_t* src, uint8_t* dst_u8, float* dst_f32, int32_t* iters, int n,
+                        int h, int w, int c, int64_t row_stride, double weight, double eps,
+                        int n_iter_max, void* workspace, size_t ws_bytes, void* stream);
 
 /* ---- quality metrics (skimage 0.14.2 measure.compare_mse / compare_psnr / compare_ssim) ---- */
 
