@@ -1012,6 +1012,12 @@ static int launch_pt_blob(dim3 grid, hipStream_t st, const uint8_t* src, float* 
 }
 
 // ---- host launchers --------------------------------------------------------------------------
+// The flat tile's LDS-DMA fetch issues 16-byte global_load_lds from the image base + 16 k: it is
+// used only from a 16-byte-aligned base (compact rows of 16 k bytes keep every image of the batch
+// there); a base at 8 mod 16 fetches the same tile through registers (16-byte buffer loads, which
+// the stripe form issues at such addresses for strided rows).
+static inline bool tile_dma_ok(const uint8_t* src) { return ((uintptr_t)src & 15) == 0; }
+
 // compact rows <= 3024 B: the LDS tile with 6-row bands (10 / 8 input rows in LDS, 30 / 24 KB per
 // workgroup, up to 5-6 workgroups per CU; band heights 4-11 measured, tools/sweep_stencil.py);
 // strided or wide rows: the stripe form from HBM; anything else the generic per-pixel kernel
@@ -1054,7 +1060,7 @@ static int launch_stencil(const uint8_t* src, uint8_t* dst, int n, int h, int w,
       hipLaunchKernelGGL((stencil_u8_lds<3, OP, NB, EPI_U8, 1>), dim3((unsigned)((int64_t)n * bands)),
                          dim3(TILE_WGT), 0, st, src, dst, h, (int)rb, nseg, seg_len, bands,
                          (int)total);
-    else if (knob("IDN_STENCIL_GLDS", 1))
+    else if (knob("IDN_STENCIL_GLDS", 1) && tile_dma_ok(src))
       hipLaunchKernelGGL((stencil_u8_lds<3, OP, NB, EPI_U8, 0, 1>), dim3((unsigned)((int64_t)n * bands)),
                          dim3(TILE_WGT), 0, st, src, dst, h, (int)rb, nseg, seg_len, bands,
                          (int)total);
@@ -1193,7 +1199,8 @@ extern "C" int idn_gaussian_blob_f32(const uint8_t* src, float* blob, int n, int
   const int64_t total = (int64_t)n * bands * nseg;
   IDN_CHECK_ARG(total < (int64_t)0x7FFFFFFF, "idn_gaussian_blob_f32: batch too large");
   const dim3 grid((unsigned)((int64_t)n * bands)), block(TILE_WGT);
-  if (ksize == 5 && knob("IDN_STENCIL_GLDS", 1))  // LDS-DMA tile fetch (as the u8 filters)
+  const bool dma = knob("IDN_STENCIL_GLDS", 1) && tile_dma_ok(src);
+  if (ksize == 5 && dma)  // LDS-DMA tile fetch (as the u8 filters)
     hipLaunchKernelGGL((stencil_u8_lds<3, OP_GAUSS5, NB, EPI_BLOB, 0, 1>), grid, block, 0, st, src,
                        nullptr, h, (int)rb, nseg, seg_len, bands, (int)total, blob, mean[0],
                        mean[1], mean[2]);
@@ -1201,7 +1208,7 @@ extern "C" int idn_gaussian_blob_f32(const uint8_t* src, float* blob, int n, int
     hipLaunchKernelGGL((stencil_u8_lds<3, OP_GAUSS5, NB, EPI_BLOB>), grid, block, 0, st, src,
                        nullptr, h, (int)rb, nseg, seg_len, bands, (int)total, blob, mean[0],
                        mean[1], mean[2]);
-  else if (knob("IDN_STENCIL_GLDS", 1))
+  else if (dma)
     hipLaunchKernelGGL((stencil_u8_lds<3, OP_GAUSS3, NB, EPI_BLOB, 0, 1>), grid, block, 0, st, src,
                        nullptr, h, (int)rb, nseg, seg_len, bands, (int)total, blob, mean[0],
                        mean[1], mean[2]);

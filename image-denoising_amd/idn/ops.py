@@ -200,8 +200,11 @@ def random_noise(x: torch.Tensor, mode: str = "gaussian", *, mean: float = 0.0, 
 
 
 def ycc_fusable(x: torch.Tensor) -> bool:
-    """random_noise_ycc takes this batch: uint8, 3 channels, an even pixel count per image"""
-    return x.dtype == torch.uint8 and x.shape[-1] == 3 and (x.shape[-3] * x.shape[-2]) % 2 == 0
+    """random_noise_ycc takes this batch: uint8, 3 channels, an even pixel count per image, and
+    not a contiguous view that starts at an odd address (idn_noise_ycc_u8 reads byte pairs; a
+    batch that is not contiguous is copied first, to an aligned address)"""
+    return (x.dtype == torch.uint8 and x.shape[-1] == 3 and (x.shape[-3] * x.shape[-2]) % 2 == 0
+            and not (x.is_contiguous() and x.data_ptr() % 2))
 
 
 def random_noise_ycc(x: torch.Tensor, mode: str = "gaussian", *, mean: float = 0.0,

@@ -31,6 +31,16 @@
  *     tested against it draw for draw (tests/test_noise_streams_gpu.py).
  *     The tuning knobs of the kernels are compile-time constants: this library reads no
  *     environment variable.
+ *   - Alignment.  A uint8 image pointer (source, destination, pattern, labels) may have any byte
+ *     alignment, a float32 / float64 pointer needs only its natural alignment (4 / 8 bytes), and
+ *     neither changes a result: the launchers pick their vector forms by the pointers they are
+ *     given and fall back to narrower accesses elsewhere (tests/test_alignment_gpu.py).  The
+ *     exceptions, each refused with a message: idn_copy_u8 (16-byte pointers and size,
+ *     IDN_EINVAL); idn_noise_ycc_u8 (2-byte u8 pointers, 16-byte out_f64, IDN_EUNSUPPORTED: use
+ *     idn_noise_u8); idn_gaussian_blob_f32 fuses only a source at 0 mod 8 with a blob at 0 mod
+ *     16 (IDN_EUNSUPPORTED otherwise: idn_gaussian_blur_u8 + idn_blob_f32 give the same blob);
+ *     the workspaces of idn_mse_u8, idn_ssim_u8 and idn_tv_chambolle_u8 are 8-byte aligned
+ *     (IDN_EINVAL).  The other workspaces are taken from the base of a device allocation.
  *   - Return IDN_OK (0) or a negative idn_status; idn_last_error() returns a thread-local
  *     message for the last failing call on the calling thread.
  *

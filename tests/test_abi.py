@@ -64,6 +64,40 @@ def test_argument_validation_without_gpu():
     assert rc == -1
 
 
+def test_alignment_rules_are_checked_on_the_host():
+    """The pointer-alignment exceptions of include/idn.h are refused before any HIP call (fake
+    addresses, never dereferenced): idn_copy_u8 (16-byte pointers and size), the fused ycc noise
+    form (2-byte u8, 16-byte float64: IDN_EUNSUPPORTED, the caller takes idn_noise_u8) and the
+    8-byte workspaces of the metrics.  tests/test_tv.py has the TV workspace."""
+    _lib_path()
+    from idn import _lib
+    lib = _lib.load()
+    A, B, O, K, WS = 0x10000, 0x20000, 0x30000, 0x40000, 0x50000
+
+    assert lib.idn_copy_u8(A, B, 0, 0, None) == 0              # nothing to copy: accepted
+    for bad in ((A + 8, B, 64), (A, B + 4, 64), (A + 1, B + 1, 64), (A, B, 40)):
+        assert lib.idn_copy_u8(*bad, 0, None) == -1, bad
+        msg = lib.idn_last_error()
+        assert b"idn_copy_u8" in msg and (b"aligned" in msg or b"multiple of 16" in msg)
+
+    def ycc(src=A, u8=None, f64=O, h=8, w=16):
+        return lib.idn_noise_ycc_u8(src, u8, f64, 1, h, w, 0, 0.0, 1.0, 1, 0, None, None, K, None)
+
+    for bad in (dict(src=A + 1), dict(f64=O + 8), dict(u8=B + 1), dict(src=A + 3, f64=O + 8),
+                dict(h=3, w=3)):
+        assert ycc(**bad) == -2, bad                            # IDN_EUNSUPPORTED
+        assert b"idn_noise_ycc_u8" in lib.idn_last_error() and b"aligned" in lib.idn_last_error()
+    assert ycc(f64=None) == -1 and b"null" in lib.idn_last_error()
+
+    n, h, w, c = 1, 16, 16, 3
+    for off in (1, 4):
+        assert lib.idn_mse_u8(A, B, O, n, h, w, c, w * c, w * c, WS + off, 1 << 20, None) == -1
+        assert b"8-byte aligned" in lib.idn_last_error()
+        assert lib.idn_ssim_u8(A, B, O, None, None, n, h, w, c, w * c, w * c, 7, WS + off, 1 << 20,
+                               None) == -1
+        assert b"8-byte aligned" in lib.idn_last_error()
+
+
 def test_missing_library_fails_loudly(tmp_path, monkeypatch):
     from idn import _lib
     monkeypatch.setattr(_lib, "LIB_PATH", tmp_path / "nope.so")
