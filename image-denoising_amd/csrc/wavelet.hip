@@ -5,29 +5,23 @@
 // 1653-1656, minibatch_before_curvelet.py:85-87.  Restated in numpy in oracle/wavelet.py (pinned
 // against pywt 1.1.1 / skimage 0.18.3 fixtures).
 //
-// Pipeline per image (all images of the batch in every launch; grid.z = image x channel):
-//   1 wl_color_minmax  per-channel fp64 min / max of the YCbCr image (BGR data treated as RGB,
-//                   as the reference does); the YCbCr planes are never stored
-//   2 wl_dwt  x L   one separable 2-D analysis level per launch: a 256-thread workgroup stages a
-//                   (2T+F-2)^2 input tile in LDS (pywt 'symmetric' extension), filters rows, then
-//                   columns, and writes the aa / ad / da / dd bands plus the tile's sums of squares
-//                   of the three detail bands.  Level 1 stages straight from the u8 (or f64) image:
-//                   YCbCr channel + (x - min) / (max - min) normalisation on the fly.
-//   3 wl_sumsq      per detail band: add the tile partials in tile order (deterministic)
-//   4 wl_median     sigma = median(|finest dd| != 0) / 0.6744897501960817: exact radix select on
-//                   the float bits (two 11-bit passes over the band, compaction of the selected
-//                   prefix into the consumed input plane, four passes over that), + one pass for
-//                   the upper middle rank
-//   5 wl_thresh     BayesShrink t = var / sqrt(max(mean(d^2) - var, eps)) per band
-//   6 wl_idwt x L-1 synthesis levels L..2 (stage-2 valid convolution of pywt's
-//                   upsampling_convolution_valid_sf) with the soft threshold d*max(1-t/|d|, 0)
-//                   applied to every detail read; output cropped to the next level's size
-//   7 wl_idwt_final level 1 for all three channels of a pixel at once, fused with clip [0,1],
-//                   de-normalisation, YCbCr -> RGB, clip [0,1] and the U8 cast
-// Storage and arithmetic are fp64 (`wreal`): the BayesShrink threshold var/sqrt(mean(d^2) - var)
-// is ill-conditioned when a band is noise dominated, so fp32 bands moved outputs by up to 5e-5.
-// The analysis filters multiply then add (no FMA), as pywt's C loop does: a detail coefficient of
-// two equal samples is then exactly 0 (-S*x + S*x), which the "nonzero" median relies on.
+// One translation unit, three paths (the host side at the end of the file picks one):
+//   fused Haar  db1, L <= 3, sides divisible by 2^L: every level inside a 2^L x 2^L block, two
+//               passes over the image (wl_haar_*, and haar3.hpp's wl_h3_* for L = 3 on u8)
+//   streaming   bior1.5: wl_dwt_stream / wl_synth_final3, one launch per level
+//   tiled       db1 otherwise: wl_dwt_rb / wl_synth / wl_synth_final, one launch per level
+// Every path (all images of the batch in every launch) is
+//   colour range  per-channel fp64 min / max of the YCbCr image (BGR data treated as RGB, as the
+//                 reference does); the YCbCr planes are never stored
+//   analysis      levels 1..L; level 1 normalises (x - min) / (max - min) on the fly; every level
+//                 leaves per-workgroup sums of squares of its detail bands
+//   sigma         median(|finest dd| != 0) / 0.6744897501960817, exact: the finest dd keeps pywt's
+//                 fp64 op order (multiply then add, no FMA), so a detail of equal samples is 0
+//   thresholds    BayesShrink t = var / sqrt(max(mean(d^2) - var, eps)) per band, from fp64 sums
+//   synthesis     levels L..1, details soft-thresholded as they are read; level 1 is fused with
+//                 clip [0, 1], de-normalisation, YCbCr -> RGB, clip and the U8 / f32 stores
+// Bands that only continuous arithmetic reads are stored, and where measured faster computed, in
+// fp32 (wl_fband).  DESIGN.md lists the forms of the product and of the tuning library.
 #include "idn_common.hpp"
 
 #include <cmath>
@@ -117,12 +111,7 @@ struct WlStats {
   static constexpr int MX64 = 203;
 };
 constexpr int WL_EBINS = 64;  // exponent bins of |dd|: bin = clamp(exponent - (1023 - 61), 0, 63)
-__device__ __forceinline__ int wl_ebin(unsigned long long key) {
-  const int e = (int)(key >> 52) - (1023 - 61);
-  return e < 0 ? 0 : (e > WL_EBINS - 1 ? WL_EBINS - 1 : e);
-}
-
-// fine bins of |dd| keys: exponent (clamped as wl_ebin) and the top 4 mantissa bits, monotone in
+// fine bins of |dd| keys: exponent (clamped as above) and the top 4 mantissa bits, monotone in
 // the key; the clamped exponent bins keep one sub-bin
 constexpr int WL_FBINS = WL_EBINS * 16;
 __device__ __forceinline__ unsigned long long absbits(double v) {
@@ -209,9 +198,11 @@ inline WlLayout wl_layout(int n, int h, int w, int wv, int levels) {
       const int groups = (Lt.H[l] + WS_G - 1) / WS_G;
       Lt.tiles_x[l] = ws_strips(Lt.W[l]);
       Lt.bands[l] = std::min(ws_bands(n, Lt.H[l], Lt.W[l], Lt.tiles_x[l], l), groups);
-      // tuning: a fixed band count per level (bit field: level l's count in bits 8(l-1)..)
+#ifdef IDN_TUNING_BUILD
+      // a fixed band count per level (bit field: level l's count in bits 8(l-1)..)
       if (const int fb = (knob("IDN_WAVELET_BANDS", 0) >> (8 * (l - 1))) & 0xFF)
         Lt.bands[l] = std::min(fb, groups);
+#endif
       Lt.tiles[l] = Lt.tiles_x[l] * Lt.bands[l];
       const double llo = 4.0 * B1 + 4.0 * B2 + 2.0 * S2, lhi = 2.0 * S2;
       const double bound = (llo * lhi) * (llo * lhi) * std::pow(llo, 4.0 * (l - 1)) *
@@ -3618,116 +3609,323 @@ __global__ __launch_bounds__(WLM_WG) void wl_haar_median(const uint8_t* __restri
 
 #include "haar3.hpp"
 
+// ---- host side ----------------------------------------------------------------------------------
+// One launcher per kernel family (each argument list once), then the two drivers: wl_run_haar (the
+// fused path) and wl_run (one launch per level: bior1.5 streaming, db1 tiled).  The product's
+// forms are the ones written out; every branch that only a tuning knob reaches is inside
+// #ifdef IDN_TUNING_BUILD, so the product library instantiates only the kernels it can launch.
+// A knob whose value feeds an expression is read through tuned(): its default, a constant, in
+// the product library (idn_common.hpp's knob).
+constexpr auto tuned = knob;
+
+// bior1.5 with the code median: the level-1 dd band in fp32 too (the median recomputes its exact
+// values from the input, bior_dd2x2; the synthesis reads it as fp32 either way)
+static bool wl_dd32(bool bior, bool codes) {
+  return bior && codes && tuned("IDN_WAVELET_FDET", 1) && tuned("IDN_WAVELET_DD32", 1);
+}
+// band masks (wl_fband) of level l: what the analysis stores, what the synthesis loads
+static int wl_fm_analysis(const WlLayout& Lt, int l, bool dd32) {
+  if (!tuned("IDN_WAVELET_FDET", 1)) return 0;
+  return (l == 1 ? (dd32 ? 0b1110 : 0b0110) : 0b1110 | WL_FB_AIN) | (l < Lt.L ? 0b0001 : 0);
+}
+static int wl_fm_synthesis(int l, bool dd32) {
+  return !tuned("IDN_WAVELET_FDET", 1) ? 0 : l == 1 && !dd32 ? 0b0110 : 0b1110;
+}
+
+struct WlCall {  // one call's arguments as the entry point received them, the workspace regions
+  const uint8_t* src;                  // u8 input, or
+  const double* in64;                  // f64 input
+  const unsigned long long* ycc_keys;  // nullable: the colour range, already reduced
+  uint8_t* out_u8;
+  float* out_f32;
+  int64_t row_stride;
+  wreal* ws;
+  double *stats, *part;  // ws + Lt.stats_off, ws + Lt.part_off
+  hipStream_t st;
+};
+
+// ---- launchers: tiled forms ---------------------------------------------------------------------
+static void wl_clear_stats(const WlCall& C, const WlLayout& Lt) {
+  hipLaunchKernelGGL(wl_init_stats, dim3((Lt.n * WL_STATS + 255) / 256), dim3(256), 0, C.st,
+                     C.stats, Lt.n, C.ycc_keys);
+}
+static void wl_minmax_exact(const WlCall& C, const WlLayout& Lt) {
+  const int64_t np = (int64_t)Lt.h * Lt.w;
+  // a few long-lived workgroups per image: per-wave reduction + atomics are the fixed cost
+  const int gx = (int)std::min<int64_t>((np / 4 + 255) / 256, 24);
+  hipLaunchKernelGGL(wl_color_minmax, dim3(gx, Lt.n), dim3(256), 0, C.st, C.src, C.in64, Lt.h,
+                     Lt.w, C.row_stride, C.stats);
+}
+template <int SRC>
+static void dwt_rb_go(const WlCall& C, const WlLayout& Lt, int l, int emit_codes, int fmask,
+                      int coop) {
+  hipLaunchKernelGGL((wl_dwt_rb<IDN_WAVELET_DB1, SRC>), dim3(Lt.tiles[l], 1, Lt.n), dim3(256), 0,
+                     C.st, C.ws, Lt.img_floats, C.stats, l == 1 ? (size_t)0 : Lt.off_band[l - 1],
+                     Lt.H[l - 1], Lt.W[l - 1], Lt.off_band[l], Lt.H[l], Lt.W[l], Lt.tiles_x[l],
+                     C.src, C.in64, C.row_stride, C.part, Lt.part_per_img, Lt.part_tile0[l],
+                     emit_codes, fmask, coop);
+}
+// level 1 leaves the dd codes for the code median when it will run (codes)
+static void wl_tiled_analysis(const WlCall& C, const WlLayout& Lt, int l, bool codes) {
+  const int fmask = wl_fm_analysis(Lt, l, false);
+  const int coop = tuned("IDN_WAVELET_COOP", 1) ? 1 : 0;  // u8 level 1: cooperative staging
+  if (l > 1) dwt_rb_go<2>(C, Lt, l, 0, fmask, coop);
+  else if (C.in64) dwt_rb_go<1>(C, Lt, 1, codes ? 1 : 0, fmask, coop);
+  else dwt_rb_go<0>(C, Lt, 1, codes ? 1 : 0, fmask, coop);
+}
+static void wl_sum_partials(const WlCall& C, const WlLayout& Ls) {
+  hipLaunchKernelGGL(wl_sumsq, dim3(Ls.n * 3 * Ls.L * 3), dim3(256), 0, C.st, C.stats, C.part, Ls);
+}
+static void wl_thresholds(const WlCall& C, const WlLayout& Lt) {
+  hipLaunchKernelGGL(wl_thresh, dim3(Lt.n), dim3(64), 0, C.st, C.stats, Lt);
+}
+// level l >= 2: the level-(l-1) 'aa' slot (consumed by the analysis already) receives the
+// reconstruction; level 1: the output image
+template <int WV>
+static void wl_tiled_synthesis(const WlCall& C, const WlLayout& Lt, int l, int fmask) {
+  const int Hout = Lt.H[l - 1], Wout = Lt.W[l - 1];
+  const int tx = (Wout + ST_O - 1) / ST_O, ty = (Hout + ST_O - 1) / ST_O;
+  if (l >= 2)
+    hipLaunchKernelGGL((wl_synth<WV>), dim3(tx * ty, Lt.n * 3), dim3(256), 0, C.st, C.ws,
+                       Lt.img_floats, C.stats, l, Lt.L, Lt.off_band[l], Lt.H[l], Lt.W[l],
+                       Lt.off_band[l - 1], Hout, Wout, (size_t)4 * Hout * Wout, tx, fmask);
+  else
+    hipLaunchKernelGGL((wl_synth_final<WV>), dim3(tx * ty, Lt.n), dim3(256), 0, C.st, C.ws,
+                       Lt.img_floats, C.stats, Lt.L, Lt.off_band[1], Lt.H[1], Lt.W[1], Lt.h, Lt.w,
+                       tx, C.out_u8, C.row_stride, C.out_f32, fmask);
+}
+
+// ---- launchers: streaming forms (bior1.5) -------------------------------------------------------
+template <int SRC, typename TL, typename TH, int FM, int CODES>
+static void dwt_stream_go(const WlCall& C, const WlLayout& Lt, int l, int emit, int fm) {
+  const int sw = ws_sw(Lt.W[l]);
+  const int strips = Lt.tiles_x[l], bands = Lt.bands[l], groups = (Lt.H[l] + WS_G - 1) / WS_G;
+  const dim3 grid((unsigned)(strips * bands), 1, (unsigned)Lt.n);
+  const dim3 blk((unsigned)((2 * sw + 8 + 63) / 64 * 64));
+  hipLaunchKernelGGL((wl_dwt_stream<SRC, TL, TH, FM, CODES>), grid, blk, 0, C.st, C.ws,
+                     Lt.img_floats, C.stats, l == 1 ? (size_t)0 : Lt.off_band[l - 1], Lt.H[l - 1],
+                     Lt.W[l - 1], Lt.off_band[l], Lt.H[l], Lt.W[l], sw, strips, bands, groups,
+                     C.src, C.in64, C.row_stride, C.part, Lt.part_per_img, Lt.part_tile0[l], emit,
+                     fm, Lt.sq_grid[l]);
+}
+// The band masks a source can meet, as compile-time constants (fm's bit 4 = WL_FB_AIN chose SRC 3
+// and is not the kernel's); anything else through the runtime-mask instance.
+template <int SRC, typename TL, typename TH>
+static void dwt_stream_pick(const WlCall& C, const WlLayout& Lt, int l, int emit, int fm) {
+  const int fmb = fm & 0b1111;
+  if constexpr (SRC == 3) {  // fp32 'aa' in: fp32 bands out (all but the coarsest 'aa'), no codes
+    if (fmb == 0b1111) dwt_stream_go<3, TL, TH, 0b1111, 0>(C, Lt, l, emit, fm);
+    else dwt_stream_go<3, TL, TH, 0b1110, 0>(C, Lt, l, emit, fm);
+  } else {
+    if constexpr (SRC == 0 || SRC == 1)
+      if (fmb == 0b1111 && emit) return dwt_stream_go<SRC, TL, TH, 0b1111, 1>(C, Lt, l, emit, fm);
+    if constexpr (SRC == 0) {
+      if (fmb == 0b1110 && emit) return dwt_stream_go<0, TL, TH, 0b1110, 1>(C, Lt, l, emit, fm);
+#ifdef IDN_TUNING_BUILD  // codes with the level-1 dd in fp64: IDN_WAVELET_DD32=0
+      if (fmb == 0b0111 && emit) return dwt_stream_go<0, TL, TH, 0b0111, 1>(C, Lt, l, emit, fm);
+      if (fmb == 0b0110 && emit) return dwt_stream_go<0, TL, TH, 0b0110, 1>(C, Lt, l, emit, fm);
+#endif
+    }
+    dwt_stream_go<SRC, TL, TH, -1, -1>(C, Lt, l, emit, fm);
+  }
+}
+// Level 1 reads the image (u8 or f64), normalises in fp64 and keeps the highpass path in fp64
+// (the finest dd's exact zeros); its lowpass path, and both paths of the deeper levels (fp32 'aa'
+// in), run in fp32.  Level 1 leaves the dd codes for the code median when it will run (codes).
+static void wl_stream_analysis(const WlCall& C, const WlLayout& Lt, int l, bool codes) {
+  const bool dd32 = wl_dd32(true, codes);
+  const int fm = wl_fm_analysis(Lt, l, dd32), emit = (l == 1 && codes) ? 1 : 0;
+#ifdef IDN_TUNING_BUILD
+  // IDN_WAVELET_A32 bit 0: level 1's lowpass path in fp32; bit 1: deeper levels in fp32;
+  // bit 2 (with bit 0, u8 input and the code median): level 1's normalisation and highpass
+  // in fp32 too, the codes from exact integer keys (wl_dwt_stream's N32; sigma bit-identical
+  // by test, but 1041 vs 849 us per 256 images: gfx950 issues fp64 FMA at the fp32 rate, and
+  // the key staging adds instructions and registers -- profiles/r06/wavelet/n32_ab.txt)
+  const int a32 = knob("IDN_WAVELET_A32", 3);
+  const bool f1 = (a32 & 1) != 0, fd = (a32 & 2) != 0;
+  if (l > 1 && !(fm & WL_FB_AIN))  // IDN_WAVELET_FDET=0: the level above's 'aa' is fp64
+    return fd ? dwt_stream_pick<2, float, float>(C, Lt, l, 0, fm)
+              : dwt_stream_pick<2, wreal, wreal>(C, Lt, l, 0, fm);
+  if (l > 1 && !fd) return dwt_stream_pick<3, wreal, wreal>(C, Lt, l, 0, fm);
+  if (l == 1 && !f1)
+    return C.in64 ? dwt_stream_pick<1, wreal, wreal>(C, Lt, 1, emit, fm)
+                  : dwt_stream_pick<0, wreal, wreal>(C, Lt, 1, emit, fm);
+  if (l == 1 && !C.in64 && (a32 & 4) && emit && dd32)  // N32: codes, dd in fp32 (1110 / 1111)
+    return (fm & 1) ? dwt_stream_go<0, float, float, 0b1111, 1>(C, Lt, 1, emit, fm)
+                    : dwt_stream_go<0, float, float, 0b1110, 1>(C, Lt, 1, emit, fm);
+#endif
+  if (l > 1) dwt_stream_pick<3, float, float>(C, Lt, l, 0, fm);
+  else if (C.in64) dwt_stream_pick<1, float, wreal>(C, Lt, 1, emit, fm);
+  else dwt_stream_pick<0, float, wreal>(C, Lt, 1, emit, fm);
+}
+// IDN_WAVELET_SSTREAM bit 0: level 1 streams, bit 1: the deeper levels (else the tiled form)
+static bool wl_stream_synthesis_on(int l) {
+  return (tuned("IDN_WAVELET_SSTREAM", 3) & (l == 1 ? 1 : 2)) != 0;
+}
+// wl_fm_synthesis, and bit 0 where level l + 1's synthesis left its reconstruction in this level's
+// 'aa' slot as fp32
+static int wl_stream_fm_synthesis(const WlLayout& Lt, int l, bool codes) {
+  const bool aa32 = l < Lt.L && wl_stream_synthesis_on(l + 1) && tuned("IDN_WAVELET_S32", 1);
+  return wl_fm_synthesis(l, wl_dd32(true, codes)) | (aa32 ? 0b0001 : 0);
+}
+// FINAL: level 1 to the output image; else the reconstruction (fp32) into level l - 1's 'aa' slots
+template <int FM, bool FINAL>
+static void synth3_go(const WlCall& C, const WlLayout& Lt, int l) {
+  const int Hout = Lt.H[l - 1], Wout = Lt.W[l - 1];
+  const int strips = s3_strips(Wout), sw = s3_sw(Wout);
+  // the band count from the measured residency of one instance per kind
+  const void* occ = FINAL ? reinterpret_cast<const void*>(&wl_synth_final3<0b0111, true>)
+                          : reinterpret_cast<const void*>(&wl_synth_final3<0b1111, false>);
+  const int bands = ss_bands_occ(Lt.n, (Hout + 1) / 2, strips, occ, S3_T);
+  hipLaunchKernelGGL((wl_synth_final3<FM, FINAL>), dim3((unsigned)(strips * bands), 1, (unsigned)Lt.n),
+                     dim3(S3_T), 0, C.st, C.ws, Lt.img_floats, C.stats, Lt.L, Lt.off_band[l],
+                     Lt.H[l], Lt.W[l], Hout, Wout, sw, strips, bands,
+                     FINAL ? C.out_u8 : (uint8_t*)nullptr, C.row_stride,
+                     FINAL ? C.out_f32 : (float*)nullptr, l, FINAL ? (size_t)0 : Lt.off_band[l - 1],
+                     FINAL ? (size_t)0 : (size_t)4 * Hout * Wout);
+}
+#ifdef IDN_TUNING_BUILD
+template <bool FINAL, typename T>
+static void synth_stream_go(const WlCall& C, const WlLayout& Lt, int l, int fm) {
+  const int Hout = Lt.H[l - 1], Wout = Lt.W[l - 1];
+  const int strips = ss_strips(Wout), sw = ss_sw(Wout);
+  const int bands = ss_bands_occ(Lt.n, (Hout + 1) / 2, strips,
+                                 reinterpret_cast<const void*>(&wl_synth_stream<false, float>), SS_MAXT);
+  hipLaunchKernelGGL((wl_synth_stream<FINAL, T>), dim3((unsigned)(strips * bands), 1, (unsigned)Lt.n),
+                     dim3(SS_MAXT), 0, C.st, C.ws, Lt.img_floats, C.stats, l, Lt.L, Lt.off_band[l],
+                     Lt.H[l], Lt.W[l], FINAL ? (size_t)0 : Lt.off_band[l - 1], Hout, Wout,
+                     FINAL ? (size_t)0 : (size_t)4 * Hout * Wout, fm, sw, strips, bands,
+                     FINAL ? C.out_u8 : (uint8_t*)nullptr, C.row_stride,
+                     FINAL ? C.out_f32 : (float*)nullptr);
+}
+#endif
+// fp32, three channels per thread, the level's band masks as compile-time constants
+static void wl_stream_synthesis(const WlCall& C, const WlLayout& Lt, int l, bool codes) {
+  const int fm = wl_stream_fm_synthesis(Lt, l, codes);
+#ifdef IDN_TUNING_BUILD
+  // IDN_WAVELET_S32=0: fp64 arithmetic; IDN_WAVELET_S3=0: a channel per thread (wl_synth_stream);
+  // IDN_WAVELET_S3D=w: that form too at the deeper levels whose output is narrower than w
+  // (measured 2.93 -> 2.85 ms per 256 images for wl_synth_final3 at levels >= 2, and no better
+  // with a width floor of 200 or 384: profiles/r03/wavelet/s3d_ab.txt)
+  const bool s32 = knob("IDN_WAVELET_S32", 1) != 0;
+  const bool s3 = s32 && knob("IDN_WAVELET_S3", 1) != 0 &&
+                  (l >= 2 ? Lt.W[l - 1] >= knob("IDN_WAVELET_S3D", 0) && (fm == 0b1111 || fm == 0b1110)
+                          : (fm & 0b0110) == 0b0110);
+  if (!s3 && l >= 2)
+    return s32 ? synth_stream_go<false, float>(C, Lt, l, fm)
+               : synth_stream_go<false, wreal>(C, Lt, l, fm);
+  if (!s3)
+    return s32 ? synth_stream_go<true, float>(C, Lt, 1, fm)
+               : synth_stream_go<true, wreal>(C, Lt, 1, fm);
+#endif
+  if (l >= 2 && fm == 0b1111) synth3_go<0b1111, false>(C, Lt, l);
+  else if (l >= 2) synth3_go<0b1110, false>(C, Lt, l);
+  else if (fm == 0b1111) synth3_go<0b1111, true>(C, Lt, 1);
+  else if (fm == 0b1110) synth3_go<0b1110, true>(C, Lt, 1);
+  else if (fm == 0b0111) synth3_go<0b0111, true>(C, Lt, 1);
+  else synth3_go<0b0110, true>(C, Lt, 1);
+}
+
+// ---- launchers: fused Haar forms and the code medians ------------------------------------------
+template <int L, bool BAND, bool BIOR>
+static void median_go(const WlCall& C, const WlLayout& Lt, const double* part, const WlLayout& Ls) {
+  hipLaunchKernelGGL((wl_haar_median<L, BAND, BIOR>), dim3(Lt.n * 3), dim3(WLM_WG), 0, C.st, C.src,
+                     C.in64, C.row_stride, C.ws, Lt.img_floats, C.stats, Lt, part, Ls);
+}
+template <bool GEN>
+static void h3_synth_go(const WlCall& C, const WlLayout& Lt) {
+  hipLaunchKernelGGL(wl_h3_synth<GEN>, dim3(h3_strips(Lt.w) * h3s_chunks(Lt.h), Lt.n),
+                     dim3(WLH_WG), 0, C.st, C.src, Lt.h, Lt.w, C.row_stride,
+                     (const double*)C.stats, C.out_u8, C.out_f32);
+}
+// the dword-store form takes a dword-aligned u8 output alone
+static void h3_synthesis(const WlCall& C, const WlLayout& Lt) {
+  if (C.out_f32 || !C.out_u8 || ((uintptr_t)C.out_u8 & 3) != 0) h3_synth_go<true>(C, Lt);
+  else h3_synth_go<false>(C, Lt);
+}
+template <int L, bool S32>
+static void synth_int_go(const WlCall& C, const WlLayout& Lt, int nwg) {
+  hipLaunchKernelGGL((wl_haar_synth_int<L, S32>), dim3(nwg, Lt.n), dim3(WLH_WG), 0, C.st, C.src,
+                     Lt.h, Lt.w, C.row_stride, C.stats, C.out_u8, C.out_f32);
+}
+
 template <int L>
-static void wl_run_haar(const uint8_t* src, const double* in64, uint8_t* out_u8, float* out_f32,
-                        const WlLayout& Lt, int64_t row_stride, void* ws, hipStream_t st,
-                  const unsigned long long* ycc_keys = nullptr) {
-  wreal* wsf = (wreal*)ws;
-  double* stats = (double*)((char*)ws + Lt.stats_off);
-  double* part = (double*)((char*)ws + Lt.part_off);
+static void wl_run_haar(const WlCall& C, const WlLayout& Lt) {
   const int n = Lt.n;
   const int nthr = (Lt.h >> L) * (Lt.w >> L) * HaarSplit<L>::NS;
   const int nwg = (nthr + WLH_WG - 1) / WLH_WG;
   if constexpr (L == 3) {
-    // round 6 (haar3.hpp): window sample, one statistics read, sigma, one synthesis read
-    // (IDN_WAVELET_H3=0: the round-4 passes below); the window kernel also clears its image's
-    // statistics block (wl_init_stats' values)
+    // u8 input (haar3.hpp): window sample, one statistics read, sigma, one synthesis read; the
+    // window kernel also clears its image's statistics block (wl_init_stats' values)
     const int nwg1 = h3_strips(Lt.w) * h3_chunks(Lt.h);
-    if (src && !ycc_keys && knob("IDN_WAVELET_H3", 1) && (size_t)(3 * nwg1) <= Lt.part_per_img / 9) {
-      hipLaunchKernelGGL(wl_h3_window, dim3(n), dim3(H3_WIN_WG), 0, st, src, Lt.h, Lt.w, row_stride,
-                         stats, knob("IDN_WAVELET_H3FB", 0));
-      hipLaunchKernelGGL(wl_h3_stats<false>, dim3(nwg1, n), dim3(WLH_WG), 0, st, src, Lt.h, Lt.w,
-                         row_stride, wsf, Lt.img_floats, stats, part, Lt.part_per_img);
-      hipLaunchKernelGGL(wl_h3_sigma, dim3(n * 3), dim3(WLM_WG), 0, st, src, row_stride, wsf,
-                         Lt.img_floats, stats, Lt, (const double*)part, nwg1);
-      const bool gen = out_f32 || !out_u8 || ((uintptr_t)out_u8 & 3) != 0;
-      if (gen)
-        hipLaunchKernelGGL(wl_h3_synth<true>, dim3(h3_strips(Lt.w) * h3s_chunks(Lt.h), n), dim3(WLH_WG), 0, st, src, Lt.h, Lt.w,
-                           row_stride, (const double*)stats, out_u8, out_f32);
-      else
-        hipLaunchKernelGGL(wl_h3_synth<false>, dim3(h3_strips(Lt.w) * h3s_chunks(Lt.h), n), dim3(WLH_WG), 0, st, src, Lt.h,
-                           Lt.w, row_stride, (const double*)stats, out_u8, (float*)nullptr);
+    // (IDN_WAVELET_H3=0: the passes below; H3FB=1: the window's fallback, forced)
+    if (C.src && !C.ycc_keys && (size_t)(3 * nwg1) <= Lt.part_per_img / 9 &&
+        tuned("IDN_WAVELET_H3", 1)) {
+      hipLaunchKernelGGL(wl_h3_window, dim3(n), dim3(H3_WIN_WG), 0, C.st, C.src, Lt.h, Lt.w,
+                         C.row_stride, C.stats, tuned("IDN_WAVELET_H3FB", 0));
+      hipLaunchKernelGGL(wl_h3_stats<false>, dim3(nwg1, n), dim3(WLH_WG), 0, C.st, C.src, Lt.h,
+                         Lt.w, C.row_stride, C.ws, Lt.img_floats, C.stats, C.part, Lt.part_per_img);
+      hipLaunchKernelGGL(wl_h3_sigma, dim3(n * 3), dim3(WLM_WG), 0, C.st, C.src, C.row_stride, C.ws,
+                         Lt.img_floats, C.stats, Lt, (const double*)C.part, nwg1);
+      h3_synthesis(C, Lt);
       return;
     }
   }
-  hipLaunchKernelGGL(wl_init_stats, dim3((n * WL_STATS + 255) / 256), dim3(256), 0, st, stats, n,
-                     ycc_keys);
-  if (!ycc_keys) {
-    const int64_t np = (int64_t)Lt.h * Lt.w;
-    // a few long-lived workgroups per image: per-wave reduction + atomics are the fixed cost
-    int gx = (int)((np / 4 + 255) / 256);
-    if (gx > 24) gx = 24;
-    hipLaunchKernelGGL(wl_color_minmax, dim3(gx, n), dim3(256), 0, st, src, in64, Lt.h, Lt.w,
-                       row_stride, stats);
-  }
-  int nwg_a;
+  wl_clear_stats(C, Lt);
+  if (!C.ycc_keys) wl_minmax_exact(C, Lt);
+  // statistics: u8 input at L >= 2 from integer moments, else from the normalised fp64 planes
+  const bool ints = L >= 2 && C.src && tuned("IDN_WAVELET_INTSTATS", 1);
+  int nwg_a = (nthr + WLH_WG * WLH_IT - 1) / (WLH_WG * WLH_IT);
   if constexpr (L >= 2) {
-    if (src && knob("IDN_WAVELET_INTSTATS", 1)) {
+    if (ints) {
       nwg_a = (nthr + WLH_WG * WLS_IT - 1) / (WLH_WG * WLS_IT);
-      hipLaunchKernelGGL((wl_haar_stats<L>), dim3(nwg_a, n), dim3(WLH_WG), 0, st, src, Lt.h, Lt.w,
-                         row_stride, wsf, Lt.img_floats, Lt.off_band[1], stats, part,
-                         Lt.part_per_img);
-    } else {
-      nwg_a = (nthr + WLH_WG * WLH_IT - 1) / (WLH_WG * WLH_IT);
-      hipLaunchKernelGGL((wl_haar_analyze<L>), dim3(nwg_a, n), dim3(WLH_WG), 0, st, src, in64,
-                         Lt.h, Lt.w, row_stride, wsf, Lt.img_floats, Lt.off_band[1], stats, part,
+      hipLaunchKernelGGL((wl_haar_stats<L>), dim3(nwg_a, n), dim3(WLH_WG), 0, C.st, C.src, Lt.h,
+                         Lt.w, C.row_stride, C.ws, Lt.img_floats, Lt.off_band[1], C.stats, C.part,
                          Lt.part_per_img);
     }
-  } else {
-    nwg_a = (nthr + WLH_WG * WLH_IT - 1) / (WLH_WG * WLH_IT);
-    hipLaunchKernelGGL((wl_haar_analyze<L>), dim3(nwg_a, n), dim3(WLH_WG), 0, st, src, in64, Lt.h,
-                       Lt.w, row_stride, wsf, Lt.img_floats, Lt.off_band[1], stats, part,
-                       Lt.part_per_img);
   }
+  if (!ints)
+    hipLaunchKernelGGL((wl_haar_analyze<L>), dim3(nwg_a, n), dim3(WLH_WG), 0, C.st, C.src, C.in64,
+                       Lt.h, Lt.w, C.row_stride, C.ws, Lt.img_floats, Lt.off_band[1], C.stats,
+                       C.part, Lt.part_per_img);
   WlLayout Ls = Lt;  // wl_sumsq view of the fused partials: nwg per level, levels back to back
   for (int l = 1; l <= L; ++l) {
     Ls.tiles[l] = nwg_a;
     Ls.part_tile0[l] = (size_t)(l - 1) * nwg_a;
   }
-  // the median workgroups also reduce the sums of squares and set the thresholds (wl_sumsq and
-  // wl_thresh as separate launches: IDN_WAVELET_FUSETHR=0)
-  if (knob("IDN_WAVELET_FUSETHR", 1)) {
-    hipLaunchKernelGGL((wl_haar_median<L>), dim3(n * 3), dim3(WLM_WG), 0, st, src, in64, row_stride,
-                       wsf, Lt.img_floats, stats, Lt, (const double*)part, Ls);
-  } else {
-    hipLaunchKernelGGL(wl_sumsq, dim3(n * 3 * L * 3), dim3(256), 0, st, stats, part, Ls);
-    hipLaunchKernelGGL((wl_haar_median<L>), dim3(n * 3), dim3(WLM_WG), 0, st, src, in64, row_stride,
-                       wsf, Lt.img_floats, stats, Lt, (const double*)nullptr, Ls);
-    hipLaunchKernelGGL(wl_thresh, dim3(n), dim3(64), 0, st, stats, Lt);
-  }
+  // the median workgroups also reduce the sums of squares and set the thresholds
+  const bool fuse = tuned("IDN_WAVELET_FUSETHR", 1) != 0;
+#ifdef IDN_TUNING_BUILD  // IDN_WAVELET_FUSETHR=0: wl_sumsq and wl_thresh as separate launches
+  if (!fuse) wl_sum_partials(C, Ls);
+#endif
+  median_go<L, false, false>(C, Lt, fuse ? (const double*)C.part : nullptr, Ls);
+#ifdef IDN_TUNING_BUILD
+  if (!fuse) wl_thresholds(C, Lt);
+#endif
+  // synthesis: u8 input at L >= 2 from the integer combinations (L = 3: haar3.hpp's fp32 form
+  // with the level-1 groups paired), else on the normalised fp64 planes
+  const bool ints_syn = L >= 2 && C.src && tuned("IDN_WAVELET_INTSYNTH", 1);
+#ifdef IDN_TUNING_BUILD  // H3S=0 at L = 3: the round-4 kernel; HS32=0: its all-fp64 form
+  if constexpr (L >= 2)
+    if (ints_syn && !(L == 3 && knob("IDN_WAVELET_H3S", 1)))
+      return knob("IDN_WAVELET_HS32", 1) ? synth_int_go<L, true>(C, Lt, nwg)
+                                         : synth_int_go<L, false>(C, Lt, nwg);
+#endif
   if constexpr (L == 3) {
-    // round 6: fp32 synthesis with the level-1 groups paired (IDN_WAVELET_H3S=0: the round-4
-    // kernel below)
-    if (src && knob("IDN_WAVELET_INTSYNTH", 1) && knob("IDN_WAVELET_H3S", 1)) {
-      hipLaunchKernelGGL(wl_h3_consts, dim3((3 * n + 63) / 64), dim3(64), 0, st, stats, n);
-      const bool gen = out_f32 || !out_u8 || ((uintptr_t)out_u8 & 3) != 0;
-      if (gen)
-        hipLaunchKernelGGL(wl_h3_synth<true>, dim3(h3_strips(Lt.w) * h3s_chunks(Lt.h), n), dim3(WLH_WG), 0, st, src, Lt.h, Lt.w,
-                           row_stride, (const double*)stats, out_u8, out_f32);
-      else
-        hipLaunchKernelGGL(wl_h3_synth<false>, dim3(h3_strips(Lt.w) * h3s_chunks(Lt.h), n), dim3(WLH_WG), 0, st, src, Lt.h,
-                           Lt.w, row_stride, (const double*)stats, out_u8, (float*)nullptr);
-      return;
+    if (ints_syn) {
+      hipLaunchKernelGGL(wl_h3_consts, dim3((3 * n + 63) / 64), dim3(64), 0, C.st, C.stats, n);
+      return h3_synthesis(C, Lt);
     }
   }
-  if constexpr (L >= 2) {
-    if (src && knob("IDN_WAVELET_INTSYNTH", 1)) {
-      if (knob("IDN_WAVELET_HS32", 1))
-        hipLaunchKernelGGL((wl_haar_synth_int<L, true>), dim3(nwg, n), dim3(WLH_WG), 0, st, src,
-                           Lt.h, Lt.w, row_stride, stats, out_u8, out_f32);
-      else
-        hipLaunchKernelGGL((wl_haar_synth_int<L, false>), dim3(nwg, n), dim3(WLH_WG), 0, st, src,
-                           Lt.h, Lt.w, row_stride, stats, out_u8, out_f32);
-      return;
-    }
-  }
-  hipLaunchKernelGGL((wl_haar_synth<L>), dim3(nwg, n), dim3(WLH_WG), 0, st, src, in64, Lt.h,
-                     Lt.w, row_stride, stats, out_u8, out_f32);
+  if constexpr (L == 2)
+    if (ints_syn) return synth_int_go<2, true>(C, Lt, nwg);
+  hipLaunchKernelGGL((wl_haar_synth<L>), dim3(nwg, n), dim3(WLH_WG), 0, C.st, C.src, C.in64, Lt.h,
+                     Lt.w, C.row_stride, C.stats, C.out_u8, C.out_f32);
 }
 
 // the fused path applies: db1, 1 <= L <= 3, both sides divisible by 2^L, room for its partials
 static bool wl_haar_ok(int wavelet, const WlLayout& Lt, const uint8_t* src, int64_t row_stride) {
-  if (wavelet != IDN_WAVELET_DB1 || Lt.L < 1 || Lt.L > 3 || knob("IDN_WAVELET_FUSED", 1) == 0)
+  if (wavelet != IDN_WAVELET_DB1 || Lt.L < 1 || Lt.L > 3 || tuned("IDN_WAVELET_FUSED", 1) == 0)
     return false;
   const int B = 1 << Lt.L;
   if (Lt.h % B || Lt.w % B) return false;
@@ -3737,243 +3935,47 @@ static bool wl_haar_ok(int wavelet, const WlLayout& Lt, const uint8_t* src, int6
   return (int64_t)Lt.L * nwg <= (int64_t)(Lt.part_per_img / 9);
 }
 
-template <int WV>
-static int wl_run(const uint8_t* src, const double* in64, uint8_t* out_u8, float* out_f32,
-                  const WlLayout& Lt, int64_t row_stride, void* ws, hipStream_t st,
-                  const unsigned long long* ycc_keys = nullptr) {
-  wreal* wsf = (wreal*)ws;
-  double* stats = (double*)((char*)ws + Lt.stats_off);
-  const int n = Lt.n;
-  hipLaunchKernelGGL(wl_init_stats, dim3((n * WL_STATS + 255) / 256), dim3(256), 0, st, stats, n,
-                     ycc_keys);
-  if (!ycc_keys) {
-    // u8 input in whole 8x8 blocks with dword-aligned rows: the Haar path's proxy min / max
-    // (wl_h3_stats<true>: fp32 proxies, fp64 rescans of the steps near an extreme); else the
-    // fp64 chain on every pixel
-    if (src && knob("IDN_WAVELET_MMPROXY", 1) && Lt.h % 8 == 0 && Lt.w % 8 == 0 && row_stride % 4 == 0 &&
-        ((uintptr_t)src & 3) == 0) {
-      hipLaunchKernelGGL(wl_h3_stats<true>, dim3(h3_strips(Lt.w) * h3_chunks_mm(Lt.h), n), dim3(WLH_WG), 0, st,
-                         src, Lt.h, Lt.w, row_stride, wsf, Lt.img_floats, stats, (double*)nullptr,
-                         (size_t)0);
-    } else {
-      const int64_t np = (int64_t)Lt.h * Lt.w;
-      // a few long-lived workgroups per image: per-wave reduction + atomics are the fixed cost
-      int gx = (int)((np / 4 + 255) / 256);
-      if (gx > 24) gx = 24;
-      hipLaunchKernelGGL(wl_color_minmax, dim3(gx, n), dim3(256), 0, st, src, in64, Lt.h, Lt.w,
-                         row_stride, stats);
-    }
-  }
-  double* part = (double*)((char*)ws + Lt.part_off);
-  // sigma from level-1 dd codes (wl_haar_median<.., true>) when the channel's input-plane slot
-  // holds codes + keys + positions (2.25 band sizes); else the radix select over the band
+// The per-level paths: bior1.5 (streaming forms) and db1 outside the fused path (tiled forms).
+// The product's forms are the ones written out here; the tuning library's knobs swap in the A/B
+// forms, inside the launchers and in the guarded lines below.
+static void wl_run(const WlCall& C, const WlLayout& Lt, bool bior) {
+  wl_clear_stats(C, Lt);
+  // u8 input in whole 8x8 blocks with dword-aligned rows: the Haar path's proxy min / max
+  // (wl_h3_stats<true>: fp32 proxies, fp64 rescans of the steps near an extreme); else the fp64
+  // chain on every pixel
+  if (!C.ycc_keys && C.src && Lt.h % 8 == 0 && Lt.w % 8 == 0 && C.row_stride % 4 == 0 &&
+      ((uintptr_t)C.src & 3) == 0 && tuned("IDN_WAVELET_MMPROXY", 1))
+    hipLaunchKernelGGL(wl_h3_stats<true>, dim3(h3_strips(Lt.w) * h3_chunks_mm(Lt.h), Lt.n),
+                       dim3(WLH_WG), 0, C.st, C.src, Lt.h, Lt.w, C.row_stride, C.ws, Lt.img_floats,
+                       C.stats, (double*)nullptr, (size_t)0);
+  else if (!C.ycc_keys) wl_minmax_exact(C, Lt);
+  // sigma from level-1 dd codes (wl_haar_median<1, true, ..>) when the channel's input-plane slot
+  // holds codes + keys + positions (2.25 band sizes); else the radix select over the fp64 band
   const size_t bsz1 = (size_t)Lt.H[1] * Lt.W[1];
-  const bool codes = knob("IDN_WAVELET_CODEMED", 1) && (bsz1 + 3) / 4 + 2 * bsz1 <= (size_t)Lt.h * Lt.w;
-  const bool fdet = knob("IDN_WAVELET_FDET", 1) != 0;
-  // bior1.5 with the code median: the level-1 dd band in fp32 too (the median recomputes its
-  // exact values from the input, bior_dd2x2; the synthesis reads it as fp32 either way)
-  const bool dd32 = WV == IDN_WAVELET_BIOR15 && codes && fdet && knob("IDN_WAVELET_DD32", 1) != 0;
-  // band masks (wl_fband): level 1 / deeper levels, analysis stores and synthesis loads
-  auto fm_an = [&](int l) {
-    if (!fdet) return 0;
-    return (l == 1 ? (dd32 ? 0b1110 : 0b0110) : 0b1110 | WL_FB_AIN) | (l < Lt.L ? 0b0001 : 0);
-  };
-  auto fm_syn = [&](int l) { return !fdet ? 0 : (l == 1 && !dd32 ? 0b0110 : 0b1110); };
-  const int coop = knob("IDN_WAVELET_COOP", 1) ? 1 : 0;
-  const int a32 = knob("IDN_WAVELET_A32", 3);
+  const bool codes =
+      (bsz1 + 3) / 4 + 2 * bsz1 <= (size_t)Lt.h * Lt.w && tuned("IDN_WAVELET_CODEMED", 1);
   for (int l = 1; l <= Lt.L; ++l) {
-    const size_t in_off = l == 1 ? 0 : Lt.off_band[l - 1];
-    if (WV == IDN_WAVELET_BIOR15) {
-      const int sw = ws_sw(Lt.W[l]);
-      const int strips = Lt.tiles_x[l], bands = Lt.bands[l], groups = (Lt.H[l] + WS_G - 1) / WS_G;
-      const dim3 grid((unsigned)(strips * bands), 1, (unsigned)n);
-      const dim3 blk((unsigned)((2 * sw + 8 + 63) / 64 * 64));
-      const int Hi = Lt.H[l - 1], Wi = Lt.W[l - 1], emit = (l == 1 && codes) ? 1 : 0;
-      // IDN_WAVELET_A32 bit 0: level 1's lowpass path in fp32; bit 1: deeper levels in fp32;
-      // bit 2 (with bit 0, u8 input and the code median): level 1's normalisation and highpass
-      // in fp32 too, the codes from exact integer keys (wl_dwt_stream's N32; sigma bit-identical
-      // by test, but 1041 vs 849 us per 256 images: gfx950 issues fp64 FMA at the fp32 rate, and
-      // the key staging adds instructions and registers -- profiles/r06/wavelet/n32_ab.txt)
-#define IDN_WS_(SRC, TL, TH, FMC, CC, EMIT)                                                        \
-  hipLaunchKernelGGL((wl_dwt_stream<SRC, TL, TH, FMC, CC>), grid, blk, 0, st, wsf, Lt.img_floats,  \
-                     stats, in_off, Hi, Wi, Lt.off_band[l], Lt.H[l], Lt.W[l], sw, strips, bands,   \
-                     groups, src, in64, row_stride, part, Lt.part_per_img, Lt.part_tile0[l], EMIT, \
-                     fm_an(l), Lt.sq_grid[l])
-      // the product's band masks as compile-time constants (bit 4 = WL_FB_AIN is read by the
-      // launcher only); anything else (tuning forms) through the runtime-mask instance
-#define IDN_WS(SRC, TL, TH, EMIT)                                                                  \
-  do {                                                                                             \
-    const int fmb = fm_an(l) & 0b1111;                                                             \
-    if ((SRC == 0 || SRC == 1) && fmb == 0b1111 && (EMIT) == 1)                                    \
-      IDN_WS_(SRC, TL, TH, 0b1111, 1, EMIT);                                                       \
-    else if (SRC == 0 && fmb == 0b1110 && (EMIT) == 1) IDN_WS_(SRC, TL, TH, 0b1110, 1, EMIT);      \
-    else if (SRC == 0 && fmb == 0b0111 && (EMIT) == 1) IDN_WS_(SRC, TL, TH, 0b0111, 1, EMIT);      \
-    else if (SRC == 0 && fmb == 0b0110 && (EMIT) == 1) IDN_WS_(SRC, TL, TH, 0b0110, 1, EMIT);      \
-    else if (SRC == 3 && fmb == 0b1111) IDN_WS_(SRC, TL, TH, 0b1111, 0, EMIT);                     \
-    else if (SRC == 3 && fmb == 0b1110) IDN_WS_(SRC, TL, TH, 0b1110, 0, EMIT);                     \
-    else IDN_WS_(SRC, TL, TH, -1, -1, EMIT);                                                       \
-  } while (0)
-      const bool f1 = (a32 & 1) != 0, fd = (a32 & 2) != 0;
-      if (l > 1 && (fm_an(l) & WL_FB_AIN)) {
-        if (fd) IDN_WS(3, float, float, 0);
-        else IDN_WS(3, wreal, wreal, 0);
-      } else if (l > 1) {
-        if (fd) IDN_WS(2, float, float, 0);
-        else IDN_WS(2, wreal, wreal, 0);
-      } else if (in64) {
-        if (f1) IDN_WS(1, float, wreal, emit);
-        else IDN_WS(1, wreal, wreal, emit);
-      } else if (f1 && (a32 & 4) && emit && dd32) {
-        // the whole level-1 analysis in fp32, codes from the exact integer keys (N32; A/B form)
-        IDN_WS(0, float, float, emit);
-      } else {
-        if (f1) IDN_WS(0, float, wreal, emit);
-        else IDN_WS(0, wreal, wreal, emit);
-      }
-#undef IDN_WS
-#undef IDN_WS_
-    } else if (l > 1)
-      hipLaunchKernelGGL((wl_dwt_rb<WV, 2>), dim3(Lt.tiles[l], 1, n), dim3(256), 0, st, wsf, Lt.img_floats, stats,
-                         in_off, Lt.H[l - 1], Lt.W[l - 1], Lt.off_band[l], Lt.H[l], Lt.W[l],
-                         Lt.tiles_x[l], src, in64, row_stride, part, Lt.part_per_img,
-                         Lt.part_tile0[l], 0, fm_an(l), coop);
-    else if (in64)
-      hipLaunchKernelGGL((wl_dwt_rb<WV, 1>), dim3(Lt.tiles[1], 1, n), dim3(256), 0, st, wsf, Lt.img_floats, stats,
-                         in_off, Lt.H[0], Lt.W[0], Lt.off_band[1], Lt.H[1], Lt.W[1],
-                         Lt.tiles_x[1], src, in64, row_stride, part, Lt.part_per_img,
-                         Lt.part_tile0[1], codes ? 1 : 0, fm_an(1), coop);
-    else
-      hipLaunchKernelGGL((wl_dwt_rb<WV, 0>), dim3(Lt.tiles[1], 1, n), dim3(256), 0, st, wsf, Lt.img_floats, stats,
-                         in_off, Lt.H[0], Lt.W[0], Lt.off_band[1], Lt.H[1], Lt.W[1],
-                         Lt.tiles_x[1], src, in64, row_stride, part, Lt.part_per_img,
-                         Lt.part_tile0[1], codes ? 1 : 0, fm_an(1), coop);
+    if (bior) wl_stream_analysis(C, Lt, l, codes);
+    else wl_tiled_analysis(C, Lt, l, codes);
   }
-  // the code medians also reduce the sums of squares and set the thresholds (see wl_haar_median)
-  const bool fuse = codes && knob("IDN_WAVELET_FUSETHR", 1);
-  const double* part_f = fuse ? (const double*)part : nullptr;
-  if (!fuse)
-    hipLaunchKernelGGL(wl_sumsq, dim3(n * 3 * Lt.L * 3), dim3(256), 0, st, stats, part, Lt);
-  if (codes && dd32)
-    hipLaunchKernelGGL((wl_haar_median<1, true, true>), dim3(n * 3), dim3(WLM_WG), 0, st, src, in64,
-                       row_stride, wsf, Lt.img_floats, stats, Lt, part_f, Lt);
-  else if (codes)
-    hipLaunchKernelGGL((wl_haar_median<1, true>), dim3(n * 3), dim3(WLM_WG), 0, st, src, in64,
-                       row_stride, wsf, Lt.img_floats, stats, Lt, part_f, Lt);
-  else
-    hipLaunchKernelGGL(wl_median, dim3(n * 3), dim3(1024), 0, st, wsf, Lt.img_floats, stats, Lt);
-  if (!fuse) hipLaunchKernelGGL(wl_thresh, dim3(n), dim3(64), 0, st, stats, Lt);
-  // bior1.5 synthesis form per level (bit 0: level 1, bit 1: deeper levels): streaming
-  // (wl_synth_stream) or tiled (wl_synth / wl_synth_final)
-  const int sstream = WV == IDN_WAVELET_BIOR15 ? knob("IDN_WAVELET_SSTREAM", 3) : 0;
-  // streaming levels in fp32 arithmetic (wl_synth_stream<.., float>); a level >= 2 that is then
-  // stores its reconstruction as fp32, so the level below reads its 'aa' band as fp32 (bit 0)
-  const bool s32 = knob("IDN_WAVELET_S32", 1) != 0;
-  // fp32 level 1 with all three channels per thread (wl_synth_final3)
-  const bool s3 = knob("IDN_WAVELET_S3", 1) != 0;
-  // ... and at the deeper levels whose output is at least this wide (0: every level; measured
-  // 2.93 -> 2.85 ms per 256 images against wl_synth_stream<false, float> at levels >= 2, and no
-  // better with a width floor of 200 or 384: profiles/r03/wavelet/s3d_ab.txt)
-  const int s3d = knob("IDN_WAVELET_S3D", 0);
-  auto str = [&](int l) { return (sstream & (l == 1 ? 1 : 2)) != 0; };
-  auto fm_syn2 = [&](int l) { return fm_syn(l) | (l < Lt.L && str(l + 1) && s32 ? 0b0001 : 0); };
-  if (sstream) {
-    for (int l = Lt.L; l >= 1; --l) {
-      if (!str(l)) {
-        if (l >= 2) {
-          const int tx = (Lt.W[l - 1] + ST_O - 1) / ST_O, ty = (Lt.H[l - 1] + ST_O - 1) / ST_O;
-          hipLaunchKernelGGL((wl_synth<WV>), dim3(tx * ty, n * 3), dim3(256), 0, st, wsf,
-                             Lt.img_floats, stats, l, Lt.L, Lt.off_band[l], Lt.H[l], Lt.W[l],
-                             Lt.off_band[l - 1], Lt.H[l - 1], Lt.W[l - 1],
-                             (size_t)4 * Lt.H[l - 1] * Lt.W[l - 1], tx, fm_syn2(l));
-        } else {
-          const int tx = (Lt.w + ST_O - 1) / ST_O, ty = (Lt.h + ST_O - 1) / ST_O;
-          hipLaunchKernelGGL((wl_synth_final<WV>), dim3(tx * ty, n), dim3(256), 0, st, wsf,
-                             Lt.img_floats, stats, Lt.L, Lt.off_band[1], Lt.H[1], Lt.W[1], Lt.h,
-                             Lt.w, tx, out_u8, row_stride, out_f32, fm_syn2(1));
-        }
-        continue;
-      }
-      const int Hout = Lt.H[l - 1], Wout = Lt.W[l - 1];
-      const int strips = ss_strips(Wout), sw = ss_sw(Wout);
-      const int bands = ss_bands_occ(
-          n, (Hout + 1) / 2, strips,
-          reinterpret_cast<const void*>(&wl_synth_stream<false, float>), SS_MAXT);
-      const dim3 grid((unsigned)(strips * bands), 1, (unsigned)n), blk(SS_MAXT);
-      const int fm2 = fm_syn2(l);
-      if (l >= 2 && s32 && s3 && Wout >= s3d && (fm2 == 0b1111 || fm2 == 0b1110)) {
-        const int strips3 = s3_strips(Wout), sw3 = s3_sw(Wout);
-        const int bands3 = ss_bands_occ(
-            n, (Hout + 1) / 2, strips3,
-            reinterpret_cast<const void*>(&wl_synth_final3<0b1111, false>), S3_T);
-        const dim3 grid3((unsigned)(strips3 * bands3), 1, (unsigned)n);
-        if (fm2 == 0b1111)
-          hipLaunchKernelGGL((wl_synth_final3<0b1111, false>), grid3, dim3(S3_T), 0, st, wsf,
-                             Lt.img_floats, stats, Lt.L, Lt.off_band[l], Lt.H[l], Lt.W[l], Hout,
-                             Wout, sw3, strips3, bands3, (uint8_t*)nullptr, row_stride,
-                             (float*)nullptr, l, Lt.off_band[l - 1], (size_t)4 * Hout * Wout);
-        else
-          hipLaunchKernelGGL((wl_synth_final3<0b1110, false>), grid3, dim3(S3_T), 0, st, wsf,
-                             Lt.img_floats, stats, Lt.L, Lt.off_band[l], Lt.H[l], Lt.W[l], Hout,
-                             Wout, sw3, strips3, bands3, (uint8_t*)nullptr, row_stride,
-                             (float*)nullptr, l, Lt.off_band[l - 1], (size_t)4 * Hout * Wout);
-      } else if (l >= 2) {
-        if (s32)
-          hipLaunchKernelGGL((wl_synth_stream<false, float>), grid, blk, 0, st, wsf, Lt.img_floats,
-                             stats, l, Lt.L, Lt.off_band[l], Lt.H[l], Lt.W[l], Lt.off_band[l - 1],
-                             Hout, Wout, (size_t)4 * Hout * Wout, fm_syn2(l), sw, strips, bands,
-                             (uint8_t*)nullptr, row_stride, (float*)nullptr);
-        else
-          hipLaunchKernelGGL((wl_synth_stream<false>), grid, blk, 0, st, wsf, Lt.img_floats, stats,
-                             l, Lt.L, Lt.off_band[l], Lt.H[l], Lt.W[l], Lt.off_band[l - 1], Hout,
-                             Wout, (size_t)4 * Hout * Wout, fm_syn2(l), sw, strips, bands,
-                             (uint8_t*)nullptr, row_stride, (float*)nullptr);
-      } else if (s32 && s3 && (fm_syn2(1) & 0b0110) == 0b0110) {
-        const int strips3 = s3_strips(Wout), sw3 = s3_sw(Wout);
-        const int bands3 = ss_bands_occ(n, (Hout + 1) / 2, strips3,
-                                        reinterpret_cast<const void*>(&wl_synth_final3<0b0111>), S3_T);
-        const dim3 grid3((unsigned)(strips3 * bands3), 1, (unsigned)n);
-        if (fm_syn2(1) == 0b1111)
-          hipLaunchKernelGGL((wl_synth_final3<0b1111>), grid3, dim3(S3_T), 0, st, wsf,
-                             Lt.img_floats, stats, Lt.L, Lt.off_band[1], Lt.H[1], Lt.W[1], Lt.h,
-                             Lt.w, sw3, strips3, bands3, out_u8, row_stride, out_f32);
-        else if (fm_syn2(1) == 0b1110)
-          hipLaunchKernelGGL((wl_synth_final3<0b1110>), grid3, dim3(S3_T), 0, st, wsf,
-                             Lt.img_floats, stats, Lt.L, Lt.off_band[1], Lt.H[1], Lt.W[1], Lt.h,
-                             Lt.w, sw3, strips3, bands3, out_u8, row_stride, out_f32);
-        else if (fm_syn2(1) == 0b0111)
-          hipLaunchKernelGGL((wl_synth_final3<0b0111>), grid3, dim3(S3_T), 0, st, wsf,
-                             Lt.img_floats, stats, Lt.L, Lt.off_band[1], Lt.H[1], Lt.W[1], Lt.h,
-                             Lt.w, sw3, strips3, bands3, out_u8, row_stride, out_f32);
-        else
-          hipLaunchKernelGGL((wl_synth_final3<0b0110>), grid3, dim3(S3_T), 0, st, wsf,
-                             Lt.img_floats, stats, Lt.L, Lt.off_band[1], Lt.H[1], Lt.W[1], Lt.h,
-                             Lt.w, sw3, strips3, bands3, out_u8, row_stride, out_f32);
-      } else if (s32) {
-        hipLaunchKernelGGL((wl_synth_stream<true, float>), grid, blk, 0, st, wsf, Lt.img_floats,
-                           stats, 1, Lt.L, Lt.off_band[1], Lt.H[1], Lt.W[1], (size_t)0, Lt.h, Lt.w,
-                           (size_t)0, fm_syn2(1), sw, strips, bands, out_u8, row_stride, out_f32);
-      } else {
-        hipLaunchKernelGGL((wl_synth_stream<true>), grid, blk, 0, st, wsf, Lt.img_floats, stats, 1,
-                           Lt.L, Lt.off_band[1], Lt.H[1], Lt.W[1], (size_t)0, Lt.h, Lt.w, (size_t)0,
-                           fm_syn2(1), sw, strips, bands, out_u8, row_stride, out_f32);
-      }
-    }
-    return IDN_OK;
+  // the code median also reduces the sums of squares and sets the thresholds
+  const bool fuse = codes && tuned("IDN_WAVELET_FUSETHR", 1);
+  const double* part_f = fuse ? C.part : nullptr;
+  if (!fuse) wl_sum_partials(C, Lt);
+  if (!codes)
+    hipLaunchKernelGGL(wl_median, dim3(Lt.n * 3), dim3(1024), 0, C.st, C.ws, Lt.img_floats,
+                       C.stats, Lt);
+  else if (wl_dd32(bior, codes)) median_go<1, true, true>(C, Lt, part_f, Lt);
+  else median_go<1, true, false>(C, Lt, part_f, Lt);
+  if (!fuse) wl_thresholds(C, Lt);
+  for (int l = Lt.L; l >= 1; --l) {
+    if (!bior) wl_tiled_synthesis<IDN_WAVELET_DB1>(C, Lt, l, wl_fm_synthesis(l, false));
+#ifdef IDN_TUNING_BUILD
+    else if (!wl_stream_synthesis_on(l))
+      wl_tiled_synthesis<IDN_WAVELET_BIOR15>(C, Lt, l, wl_stream_fm_synthesis(Lt, l, codes));
+#endif
+    else wl_stream_synthesis(C, Lt, l, codes);
   }
-  for (int l = Lt.L; l >= 2; --l) {
-    // the level-(l-1) 'aa' slot (consumed by the analysis already) receives the reconstruction
-    const int tx = (Lt.W[l - 1] + ST_O - 1) / ST_O, ty = (Lt.H[l - 1] + ST_O - 1) / ST_O;
-    hipLaunchKernelGGL((wl_synth<WV>), dim3(tx * ty, n * 3), dim3(256), 0, st, wsf, Lt.img_floats,
-                       stats, l, Lt.L, Lt.off_band[l], Lt.H[l], Lt.W[l], Lt.off_band[l - 1],
-                       Lt.H[l - 1], Lt.W[l - 1], (size_t)4 * Lt.H[l - 1] * Lt.W[l - 1], tx, fm_syn(l));
-  }
-  {
-    const int tx = (Lt.w + ST_O - 1) / ST_O, ty = (Lt.h + ST_O - 1) / ST_O;
-    hipLaunchKernelGGL((wl_synth_final<WV>), dim3(tx * ty, n), dim3(256), 0, st, wsf,
-                       Lt.img_floats, stats, Lt.L, Lt.off_band[1], Lt.H[1], Lt.W[1], Lt.h, Lt.w,
-                       tx, out_u8, row_stride, out_f32, fm_syn(1));
-  }
-  return IDN_OK;
 }
 
 }  // namespace idn
@@ -4013,17 +4015,13 @@ static int wavelet_impl(const uint8_t* src, const double* in_f64,
   if (!workspace || ws_bytes < Lt.bytes)
     return set_error(IDN_EWORKSPACE, "idn_wavelet_denoise_u8: needs %zu workspace bytes (got %zu)",
                      Lt.bytes, ws_bytes);
-  hipStream_t st = as_stream(stream);
-  const unsigned long long* K = ycc_keys;
-  if (wl_haar_ok(wavelet, Lt, src, row_stride)) {
-    if (Lt.L == 1) wl_run_haar<1>(src, in_f64, out_u8, out_f32, Lt, row_stride, workspace, st, K);
-    else if (Lt.L == 2) wl_run_haar<2>(src, in_f64, out_u8, out_f32, Lt, row_stride, workspace, st, K);
-    else wl_run_haar<3>(src, in_f64, out_u8, out_f32, Lt, row_stride, workspace, st, K);
-  } else if (wavelet == IDN_WAVELET_DB1) {
-    wl_run<IDN_WAVELET_DB1>(src, in_f64, out_u8, out_f32, Lt, row_stride, workspace, st, K);
-  } else {
-    wl_run<IDN_WAVELET_BIOR15>(src, in_f64, out_u8, out_f32, Lt, row_stride, workspace, st, K);
-  }
+  const WlCall C{src, in_f64, ycc_keys, out_u8, out_f32, row_stride, (wreal*)workspace,
+                 (double*)((char*)workspace + Lt.stats_off),
+                 (double*)((char*)workspace + Lt.part_off), as_stream(stream)};
+  if (!wl_haar_ok(wavelet, Lt, src, row_stride)) wl_run(C, Lt, wavelet == IDN_WAVELET_BIOR15);
+  else if (Lt.L == 1) wl_run_haar<1>(C, Lt);
+  else if (Lt.L == 2) wl_run_haar<2>(C, Lt);
+  else wl_run_haar<3>(C, Lt);
   IDN_CHECK_LAUNCH("idn_wavelet_denoise_u8");
   return IDN_OK;
 }

@@ -139,6 +139,29 @@ def test_product_library_reads_no_environment():
                 assert tuning_depth is not None and tuning_depth > 0, f"{src.name}:{i}: {t}"
 
 
+def test_product_library_holds_no_tuning_only_wavelet_kernels():
+    """The wavelet's A/B forms live in the tuning library alone: the kernel handles (dynamic data
+    symbols named like their kernels) of the channel-per-thread streaming synthesis and of the
+    all-fp64 integer Haar synthesis are exported by libidn_hip_tuning.so and not by libidn_hip.so"""
+    import subprocess
+    from idn import _lib
+    tuning = Path(_lib.VARIANTS["tuning"])
+    assert tuning.exists(), "libidn_hip_tuning.so not built: __graft_entry__.build() builds both"
+    nm ="/opt/rocm/lib/llvm/bin/llvm-nm"
+    if not Path(nm).exists():
+        nm = "nm"
+
+    def defined(p):
+        return subprocess.run([nm, "-D", "--defined-only", str(p)], capture_output=True, text=True,
+                              check=True).stdout
+
+    prod, tun = defined(_lib_path()), defined(tuning)
+    assert "wl_synth_final3" in prod  # the product's form is visible this way
+    for name in ("wl_synth_stream", "wl_haar_synth_intILi2ELb0EE", "wl_haar_synth_intILi3ELb0EE"):
+        assert name in tun, name
+        assert name not in prod, name
+
+
 def test_abi_version_matches_header_and_binding():
     """IDN_ABI_VERSION (include/idn.h) == idn_abi_version() of the built library == the version
     idn/_lib.py binds; the binding refuses a library of another version"""
