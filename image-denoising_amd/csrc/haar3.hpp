@@ -1,7 +1,8 @@
 // Haar L = 3 on u8 images (BASELINE config 5's denoiser: skimage 0.14.2 denoise_wavelet(db1,
 // wavelet_levels=3), lib/roi_data_layer/minibatch_before_curvelet.py:85-87), round 6: two reads of
-// the image and one write.  Included by wavelet.hip inside namespace idn, after the shared helpers
-// (stats layout, haar_int / ycc_w, the exact dd key, select_bin / radix_pass).
+// the image and one write.  Included by wavelet_haar.hip inside namespace idn, after the shared
+// helpers (wavelet_common.hpp: stats layout, ycc_w; wavelet_sigma.hpp: the exact dd key,
+// select_bin / radix_pass; wavelet_haar.hip: haar_int).
 //
 //   wl_h3_window  reads 1/8 of the level-1 rows of every image: per channel a histogram of the
 //                 finest |T| (T = w_c . D_dd, the exact integer that the finest dd is a multiple

@@ -1,6 +1,6 @@
 // skimage rgb2ycbcr's fp64 dot products and the order-preserving u64 keys of their min / max
-// (shared by the wavelet's colour range, wavelet.hip, and the float64 noise kernel that reduces
-// that range while it writes the image, noise.hip).
+// (shared by the wavelet's colour range, wavelet_common.hpp, and the float64 noise kernel that
+// reduces that range while it writes the image, noise.hip).
 #pragma once
 
 #include "idn_common.hpp"

@@ -39,13 +39,13 @@ a knob):
                                                    src 1, 3: the general fp64 chain;
                                                    test_wavelet[bior1.5-40x64-u8] at src 1, 3:
                                                    wl_color_minmax instead of the proxy
-  wavelet.hip wl_h3_synth<true> (out_u8 & 3)       test_wavelet[db1-L3-16x24-u8] out u8 at 1, 2
-  wavelet.hip (out_u8 | row_stride) & 3 row stores test_wavelet[*] out u8 at 1, 2 (and every case of
+  wavelet_haar.hip wl_h3_synth<true> (out_u8 & 3)  test_wavelet[db1-L3-16x24-u8] out u8 at 1, 2
+  wavelet_*.hip (out_u8 | row_stride) & 3 stores   test_wavelet[*] out u8 at 1, 2 (and every case of
                                                    odd row length at any offset)
-  wavelet.hip float output & 7 paired stores       test_wavelet[*] out f32 at 4, 12: every pair the
+  wavelet_stream.hip float out & 7 paired stores   test_wavelet[*] out f32 at 4, 12: every pair the
     (wl_synth_stream, wl_synth_final3)             aligned run stores whole is stored singly and the
                                                    other way round
-  wavelet.hip & 7 / & 15 in wl_dwt_stream          on a band in the workspace, not on a pointer of
+  wavelet_stream.hip & 7 / & 15 in wl_dwt_stream   on a band in the workspace, not on a pointer of
                                                    the caller: the band's width decides
                                                    (test_wavelet[bior1.5-37x53-*]: 30-wide bands)
   jpeg.hip output pointer & 7, & 3                 test_jpeg_decode_out at 4 (dword stores), 1 (bytes)

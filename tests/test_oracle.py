@@ -190,7 +190,7 @@ def test_bior15_finest_dd_is_a_2x2_combination(shape):
     """bior1.5's analysis highpass has two taps, so each level-1 dd coefficient (pywt dwtn: axis 0,
     then axis 1) is the 2x2 combination of the samples at rows 2i-4, 2i-3 and columns 2j-4, 2j-3
     ('symmetric' indices) in the op order (-S * odd) + (S * even): bit for bit.  The HIP sigma median
-    recomputes its candidates this way (csrc/wavelet.hip bior_dd2x2) instead of storing the fp64
+    recomputes its candidates this way (csrc/wavelet_sigma.hpp bior_dd2x2) instead of storing the fp64
     band."""
     from oracle.wavelet import _S, _sym_index, dwtn
     x = np.random.RandomState(sum(shape)).rand(*shape)

@@ -1,4 +1,4 @@
-// Empirical check behind wavelet.hip haar_row4_c (verification aid, not product code): the
+// Empirical check behind wavelet_haar.hip haar_row4_c (verification aid, not product code): the
 // Markstein-corrected quotient q1 = fma(fma(-q0, b, a), r, q0), q0 = a*r, r = 1/b equals the IEEE
 // quotient a/b for every u8 triple's normalised YCbCr value over 24 channel ranges.
 //   gcc -O2 -ffp-contract=off -o /tmp/check_div tools/check_div.c -lm && /tmp/check_div
