@@ -93,6 +93,9 @@ SIGNATURES = {
     "idn_tv_chambolle_workspace_size": (_c_size, [_c_int, _c_int, _c_int, _c_int]),
     "idn_tv_chambolle_u8": (_c_int, [_c_u8p, _c_u8p, _c_vp, _c_vp, _c_int, _c_int, _c_int, _c_int,
                                      _c_i64, _c_dbl, _c_dbl, _c_int, _c_vp, _c_size, _c_vp]),
+    "idn_estimate_sigma_workspace_size": (_c_size, [_c_int, _c_int, _c_int, _c_int, _c_int]),
+    "idn_estimate_sigma": (_c_int, [_c_u8p, _c_f64p, _c_f64p, _c_int, _c_int, _c_int, _c_int, _c_i64,
+                                    _c_vp, _c_size, _c_vp]),
     "idn_metrics_workspace_size": (_c_size, [_c_int, _c_int, _c_int, _c_int, _c_int]),
     "idn_mse_u8": (_c_int, [_c_u8p, _c_u8p, _c_f64p, _c_int, _c_int, _c_int, _c_int, _c_i64, _c_i64,
                             _c_vp, _c_size, _c_vp]),

@@ -16,6 +16,7 @@ the OpenCV / scikit-image calls the reference makes on its preprocessing path:
   nl_means(x, h, t, s)                    cv2.fastNlMeansDenoising(x, None, h, t, s) (3.4, 8-bit)
   nl_means_colored(x, h, h_color, t, s)   cv2.fastNlMeansDenoisingColored(x, None, h, h_color, t, s)
   denoise_tv_chambolle(x, weight, eps, n) skimage.restoration.denoise_tv_chambolle (0.14.2)
+  estimate_sigma(x, average_sigmas)       skimage.restoration.estimate_sigma (multichannel=True)
 
 There is no CPU path: a CPU tensor raises, a missing library raises.
 """
@@ -915,6 +916,60 @@ def denoise_tv_chambolle(x: torch.Tensor, weight: float = 0.1, eps: float = 2e-4
     if return_iters:
         res.append(_finish(its, sq))
     return res[0] if len(res) == 1 else tuple(res)
+
+
+# ---- noise level -------------------------------------------------------------------------------
+
+def _sigma_check(x) -> None:
+    """argument errors of estimate_sigma, raised before the device is looked at"""
+    name = "estimate_sigma"
+    if not isinstance(x, torch.Tensor):
+        raise TypeError(f"{name}: expected a torch.Tensor, got {type(x).__name__}")
+    if x.dtype not in (torch.uint8, torch.float64):
+        raise TypeError(f"{name}: expected uint8 or float64 images, got {x.dtype}")
+    if x.dim() not in (3, 4):
+        raise ValueError(f"{name}: expected (H,W,C) or (N,H,W,C), got shape {tuple(x.shape)}")
+    if x.shape[-1] not in (1, 3):
+        raise ValueError(f"{name}: 1 or 3 channels supported, got {x.shape[-1]}")
+    if x.device.type != "cuda":
+        raise ValueError(f"{name}: idn runs on the GPU only; got a {x.device} tensor "
+                         "(move it with .cuda(); there is no CPU fallback)")
+
+
+def estimate_sigma(x: torch.Tensor, average_sigmas: bool = False) -> torch.Tensor:
+    """skimage.restoration.estimate_sigma(x[i], multichannel=True, average_sigmas=...) per image:
+    the noise standard deviation of every channel, from the median absolute finest diagonal db2
+    wavelet coefficient over norm.ppf(0.75).  x: uint8 or float64, (N,)H,W,C with C 1 or 3, H and
+    W at least 4.  Returns float64 on the device: (N, C), or (C,) for one image; with
+    average_sigmas (N,) or 0-d, ((s0 + s1) + s2) / 3 as numpy's mean adds them.
+    The scale is the input's, as in skimage: a uint8 batch is estimated on 0..255 (the scale of
+    nl_means' h; divide by 255 for denoise_tv_chambolle and denoise_wavelet), a float64 batch in
+    [0, 1] on that scale.  A channel with no nonzero coefficient (an all-zero channel) gives NaN.
+    Bit-equal to the numpy float64 model tests/sigma_model.py, which is pinned bit for bit to
+    the real skimage and pywt; the same bits on every call and in every batch."""
+    _sigma_check(x)
+    xb, sq = _as_batch(x, "estimate_sigma")
+    if not xb.is_contiguous():
+        xb = xb.contiguous()
+    n, h, w, c = xb.shape
+    out = torch.empty((n, c), dtype=torch.float64, device=xb.device)
+    if n > 0:
+        lib = _lib.load()
+        is_f64 = xb.dtype == torch.float64
+        nbytes = lib.idn_estimate_sigma_workspace_size(n, h, w, c, int(is_f64))
+        ws = _workspace(nbytes, xb.device)
+        rc = lib.idn_estimate_sigma(None if is_f64 else xb.data_ptr(),
+                                    xb.data_ptr() if is_f64 else None, out.data_ptr(), n, h, w, c,
+                                    w * c, ws.data_ptr(), nbytes, _stream())
+        _lib.check(rc, "idn_estimate_sigma")
+    if average_sigmas:
+        if c == 3:
+            # a tensor divisor: torch turns a division by a Python scalar into a multiplication
+            three = torch.full((), 3.0, dtype=torch.float64, device=out.device)
+            out = ((out[:, 0] + out[:, 1]) + out[:, 2]) / three
+        else:
+            out = out[:, 0]
+    return _finish(out, sq)
 
 
 # ---- quality metrics ---------------------------------------------------------------------------

@@ -39,8 +39,8 @@
  *     IDN_EINVAL); idn_noise_ycc_u8 (2-byte u8 pointers, 16-byte out_f64, IDN_EUNSUPPORTED: use
  *     idn_noise_u8); idn_gaussian_blob_f32 fuses only a source at 0 mod 8 with a blob at 0 mod
  *     16 (IDN_EUNSUPPORTED otherwise: idn_gaussian_blur_u8 + idn_blob_f32 give the same blob);
- *     the workspaces of idn_mse_u8, idn_ssim_u8 and idn_tv_chambolle_u8 are 8-byte aligned
- *     (IDN_EINVAL).  The other workspaces are taken from the base of a device allocation.
+ *     the workspaces of idn_mse_u8, idn_ssim_u8, idn_tv_chambolle_u8 and idn_estimate_sigma are
+ *     8-byte aligned (IDN_EINVAL).  The other workspaces are taken from the base of a device allocation.
  *   - Return IDN_OK (0) or a negative idn_status; idn_last_error() returns a thread-local
  *     message for the last failing call on the calling thread.
  *
@@ -100,7 +100,8 @@ typedef enum idn_wavelet {
  *      idn_nlmeans_colored_workspace_size and idn_nlmeans_colored_u8 added (no signature
  *      changed)
  *  10  total-variation denoising: idn_tv_chambolle_workspace_size and idn_tv_chambolle_u8 added
- *      (no signature changed) */
+ *      (no signature changed); later, under the same number, the noise-level estimate:
+ *      idn_estimate_sigma_workspace_size and idn_estimate_sigma added (no signature changed) */
 #define IDN_ABI_VERSION 10
 int idn_abi_version(void);
 const char* idn_version(void);
@@ -427,6 +428,38 @@ size_t idn_tv_chambolle_workspace_size(int n, int h, int w, int c);
 int idn_tv_chambolle_u8(const uint8_t* src, uint8_t* dst_u8, float* dst_f32, int32_t* iters, int n,
                         int h, int w, int c, int64_t row_stride, double weight, double eps,
                         int n_iter_max, void* workspace, size_t ws_bytes, void* stream);
+
+/* ---- noise level (skimage restoration.estimate_sigma, unchanged 0.14.2 .. 0.18.3) ------------ */
+
+/* Not a reference interface: measures the noise of the batch a pipeline is handed, so that the
+ * strengths of the denoisers above need not be guessed.  dst[i*c + ch] =
+ * estimate_sigma(x[i][..., ch]): the median of |d| over the coefficients d != 0 of the finest
+ * diagonal db2 detail band (pywt.dwtn(plane, 'db2')['dd'], symmetric extension), divided by
+ * norm.ppf(0.75) = 0.6744897501960817.  Exactly one of src_u8 / src_f64 is given, the other is
+ * NULL; the plane is taken as float64 as it is (no division by 255), so the result is on the
+ * input's scale.  row_stride counts elements of the source (bytes / doubles), >= w*c.
+ * tests/sigma_model.py restates pywt's arithmetic in numpy float64, tap order included, and is
+ * the definition; tests/golden/sigma.npz pins it bit for bit to the real skimage and pywt.  The
+ * kernels compute every coefficient in fp64 in that order and select the median exactly on the
+ * key bits: dst is bit-equal to the model, the same bits on every call and in every batch.  A
+ * plane without a nonzero coefficient gives NaN.  A flat region of a nonzero value gives
+ * coefficients of about 1e-31, not zeros, and they count (as in pywt).  Non-finite float64 input
+ * gives an unspecified value; no access leaves the buffers.
+ * The band is not stored: up to six passes recompute it from the image (three for noise-like
+ * images), each followed by one small launch per plane.  Stream-ordered and capture-safe: no
+ * allocation, copy or synchronisation inside.
+ * workspace: idn_estimate_sigma_workspace_size(n, h, w, c, is_f64) bytes (0 for n <= 0, h or
+ *   w < 4, c not 1 or 3; additive in n), 8-byte aligned, contents irrelevant on entry: counters
+ *   and a short key list, 32840 bytes per (image, channel), whatever the image size.
+ * IDN_EINVAL: both or neither source given, null dst, src_f64 or dst not 8-byte aligned, n < 0,
+ *   h or w < 1, c not 1 or 3, row_stride < w*c, workspace not 8-byte aligned.  IDN_EUNSUPPORTED:
+ *   h or w < 4 (the extension would reflect twice).  IDN_EWORKSPACE: workspace missing or too
+ *   small.  n == 0 returns IDN_OK without a launch.  Every argument check runs before any HIP
+ *   call. */
+size_t idn_estimate_sigma_workspace_size(int n, int h, int w, int c, int is_f64);
+int idn_estimate_sigma(const uint8_t* src_u8, const double* src_f64, double* dst, int n, int h,
+                       int w, int c, int64_t row_stride, void* workspace, size_t ws_bytes,
+                       void* stream);
 
 /* ---- quality metrics (skimage 0.14.2 measure.compare_mse / compare_psnr / compare_ssim) ---- */
 
