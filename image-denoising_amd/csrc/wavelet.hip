@@ -5,7 +5,8 @@
 // 1653-1656, minibatch_before_curvelet.py:85-87.  Restated in numpy in oracle/wavelet.py (pinned
 // against pywt 1.1.1 / skimage 0.18.3 fixtures).
 //
-// Three paths, a translation unit each (the host side at the end of this file picks one):
+// Three paths, a translation unit each (the host side at the end of this file picks one; every
+// other option of denoise_wavelet has a unit and an entry point of its own, wavelet_general.hip):
 //   fused Haar  db1, L <= 3, sides divisible by 2^L: every level inside a 2^L x 2^L block, two
 //               passes over the image (wl_haar_*, and haar3.hpp's wl_h3_* for L = 3 on u8)
 //               -- wavelet_haar.hip, which also has what the other two paths launch of it:

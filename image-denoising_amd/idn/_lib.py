@@ -79,6 +79,10 @@ SIGNATURES = {
                                          _c_int, _c_int, _c_vp, _c_size, _c_vp]),
     "idn_wavelet_workspace_size": (_c_size, [_c_int, _c_int, _c_int, _c_int, _c_int]),
     "idn_wavelet_stats_offset": (_c_size, [_c_int, _c_int, _c_int, _c_int, _c_int]),
+    "idn_wavelet_general_workspace_size": (_c_size, [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int]),
+    "idn_wavelet_denoise_general": (_c_int, [_c_u8p, _c_f64p, _c_u8p, _c_vp, _c_int, _c_int, _c_int,
+                                             _c_int, _c_i64, _c_int, _c_int, _c_int, _c_int, _c_int,
+                                             _c_f64p, _c_vp, _c_size, _c_vp]),
     "idn_gaussian_blur_f64": (_c_int, [_c_vp, _c_vp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_vp]),
     "idn_box_blur_f64": (_c_int, [_c_vp, _c_vp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_vp]),
     "idn_nlmeans_weights": (_c_int, [_c_dbl, _c_int, _c_int, _c_int, _c_vp, _c_int, _c_vp, _c_vp, _c_vp]),

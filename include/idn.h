@@ -76,11 +76,24 @@ typedef enum idn_noise_kind {
   IDN_NOISE_POISSON = 3   /* out = clip(Poisson(x*vals)/vals, 0, 1), vals per image    */
 } idn_noise_kind;
 
-/* wavelet families for idn_wavelet_denoise_u8 */
+/* wavelet families: idn_wavelet_denoise_u8 / _ycc take the first two, idn_wavelet_denoise_general
+ * all five */
 typedef enum idn_wavelet {
   IDN_WAVELET_DB1 = 0,    /* Haar ('db1', skimage default)                           */
-  IDN_WAVELET_BIOR15 = 1  /* 'bior1.5' (the reference's in-branch choice)             */
+  IDN_WAVELET_BIOR15 = 1, /* 'bior1.5' (the reference's in-branch choice)             */
+  IDN_WAVELET_DB2 = 2,    /* 'db2'   (F = 4; the wavelet of idn_estimate_sigma)       */
+  IDN_WAVELET_SYM4 = 3,   /* 'sym4'  (F = 8)                                          */
+  IDN_WAVELET_COIF5 = 4   /* 'coif5' (F = 30; the reference's older recipe)           */
 } idn_wavelet;
+/* threshold selection and shrinkage of idn_wavelet_denoise_general */
+typedef enum idn_wavelet_method {
+  IDN_WAVELET_BAYES = 0,  /* per band t = var / sqrt(max(mean(d^2) - var, eps))       */
+  IDN_WAVELET_VISU = 1    /* one threshold sigma sqrt(2 log(h w))                      */
+} idn_wavelet_method;
+typedef enum idn_wavelet_mode {
+  IDN_WAVELET_SOFT = 0,   /* pywt.threshold(d, t, 'soft')                             */
+  IDN_WAVELET_HARD = 1    /* d where |d| >= t, else 0                                 */
+} idn_wavelet_mode;
 
 /* ---- library ------------------------------------------------------------------------- */
 /* ABI version of this header; idn_abi_version() returns the library's.  A caller (the ctypes
@@ -101,7 +114,11 @@ typedef enum idn_wavelet {
  *      changed)
  *  10  total-variation denoising: idn_tv_chambolle_workspace_size and idn_tv_chambolle_u8 added
  *      (no signature changed); later, under the same number, the noise-level estimate:
- *      idn_estimate_sigma_workspace_size and idn_estimate_sigma added (no signature changed) */
+ *      idn_estimate_sigma_workspace_size and idn_estimate_sigma added (no signature changed);
+ *      and the wavelet denoiser's options: idn_wavelet_general_workspace_size and
+ *      idn_wavelet_denoise_general added, with IDN_WAVELET_DB2 / SYM4 / COIF5 and the enums
+ *      idn_wavelet_method and idn_wavelet_mode (no signature changed; the earlier wavelet entry
+ *      points reject the new wavelets) */
 #define IDN_ABI_VERSION 10
 int idn_abi_version(void);
 const char* idn_version(void);
@@ -312,6 +329,29 @@ size_t idn_wavelet_workspace_size(int n, int h, int w, int wavelet, int levels);
 /* diagnostics: byte offset in the workspace of the per-image statistics blocks (256 doubles per
  * image: channel sums of squared details, sigma medians, thresholds) after a call */
 size_t idn_wavelet_stats_offset(int n, int h, int w, int wavelet, int levels);
+
+/* The denoiser with every option: per image skimage 0.14.2's
+ *   denoise_wavelet(img, sigma, wavelet, mode, wavelet_levels=levels, multichannel=True,
+ *                   convert2ycbcr=convert2ycbcr, method=method)
+ * (c = 1 with convert2ycbcr = 0: multichannel=False on the 2-D image), then the u8 cast.
+ * Exactly one of src (u8, rows of row_stride >= w*c bytes) and in_f64 (dense n*h*w*c, values in
+ * [0, 1]) is given; out_u8 (rows of row_stride bytes) and / or out_f32 (dense) receive the result.
+ * c is 1 or 3; convert2ycbcr needs c = 3.  wavelet: any idn_wavelet, extension 'symmetric';
+ * levels <= 0 selects max(dwt_max_level - 3, 1), at most 10 levels.  method: idn_wavelet_method,
+ * mode: idn_wavelet_mode.  sigma_dev: null (sigma = median(|dd_1| != 0) / 0.6745 per channel) or
+ * n*c doubles in device memory, sigma of image i channel k at [i*c + k], read on the device; with
+ * convert2ycbcr it applies to the normalised Y / Cb / Cr channel.  convert2ycbcr = 0 transforms
+ * each channel of the float image as it is and clips once to [0, 1].  A channel without a finite
+ * sigma (no nonzero dd_1) gives 0.  Every band is fp64 and the analysis keeps pywt's operation
+ * order; |out - reference| <= 1e-5 before the cast.  With the options of idn_wavelet_denoise_u8
+ * (BAYES, SOFT, no sigma, convert2ycbcr) it computes what that function computes, on kernels of
+ * its own, slower.  No allocation, stream-ordered. */
+size_t idn_wavelet_general_workspace_size(int n, int h, int w, int c, int wavelet, int levels);
+int idn_wavelet_denoise_general(const uint8_t* src, const double* in_f64, uint8_t* out_u8,
+                                float* out_f32, int n, int h, int w, int c, int64_t row_stride,
+                                int wavelet, int levels, int method, int mode, int convert2ycbcr,
+                                const double* sigma_dev, void* workspace, size_t ws_bytes,
+                                void* stream);
 
 /* ---- float64 filters (the reference's quirk branches blur random_noise's float64 output) -- */
 
