@@ -20,7 +20,7 @@ OpenCV 3.4.2 (`/root/reference/requirements.txt:89`; call sites `lib/model/test.
                 entry of a tag wins; Orientation (0x0112) = the u16 at entry + 8.  32-bit offset
                 arithmetic wraps like exif.cpp's uint32_t.
 
-The device restatement is `jpg_exif_orientation` in image-denoising_amd/csrc/jpeg.hip; tests check
+The library's restatement is `jpg_exif_orientation` in image-denoising_amd/csrc/jpeg_host.hpp; tests check
 the two against each other and against Pillow's own reading of the tag (Image.getexif)."""
 import numpy as np
 

@@ -187,12 +187,14 @@ def test_docs_name_only_declared_entry_points():
 
 
 def test_header_jpeg_support_matches_decoder():
-    """include/idn.h's list of what the JPEG decoder takes / rejects agrees with csrc/jpeg.hip: a
-    frame type the parser accepts (SOF0 / SOF1 / SOF2 cases of its marker switch) may not appear
-    among the header's unsupported kinds, and one it rejects must"""
+    """include/idn.h's list of what the JPEG decoder takes / rejects agrees with the decoder
+    (csrc/jpeg_host.hpp: the parser; csrc/jpeg_pixels.hip: jpg_smooth): a frame type the parser
+    accepts (SOF0 / SOF1 / SOF2 cases of its marker switch) may not appear among the header's
+    unsupported kinds, and one it rejects must"""
     import re
     hdr = (ROOT / "include" / "idn.h").read_text()
-    src = (ROOT / "image-denoising_amd" / "csrc" / "jpeg.hip").read_text()
+    csrc = ROOT / "image-denoising_amd" / "csrc"
+    src = (csrc / "jpeg_host.hpp").read_text()
     info = hdr[hdr.index("/* Header of one JPEG file"):hdr.index("int idn_jpeg_info")]
     taken, unsupported = info.split("IDN_EUNSUPPORTED", 1)
     accepted_sof = set(re.findall(r"case 0x(C[0-9A-F])", src.split("// DHT")[0]))
@@ -204,6 +206,7 @@ def test_header_jpeg_support_matches_decoder():
     assert "multi-scan" not in unsupported and "several scans" in taken
     assert "lossless" in unsupported and "hierarchical" in unsupported
     # block smoothing (jpg_smooth) is restated: the header lists it among what is taken
-    assert "jpg_smooth(D" in src and "block-smoothed" in taken and "smooth" not in unsupported
+    assert "jpg_smooth(D" in (csrc / "jpeg_pixels.hip").read_text()
+    assert "block-smoothed" in taken and "smooth" not in unsupported
     dec = hdr[hdr.index("/* cv2.imread(path) (IMREAD_COLOR) of n"):hdr.index("int idn_jpeg_decode_u8")]
     assert "progressive" in dec and "baseline JPEG files" not in dec

@@ -48,7 +48,7 @@ a knob):
   wavelet_stream.hip & 7 / & 15 in wl_dwt_stream   on a band in the workspace, not on a pointer of
                                                    the caller: the band's width decides
                                                    (test_wavelet[bior1.5-37x53-*]: 30-wide bands)
-  jpeg.hip output pointer & 7, & 3                 test_jpeg_decode_out at 4 (dword stores), 1 (bytes)
+  jpeg_pixels.hip output pointer & 7, & 3          test_jpeg_decode_out at 4 (dword stores), 1 (bytes)
   bilateral_u8.hip output pointer & 1              test_bilateral at (0,1) (3,5)
 
 Kernels that promise any alignment and had only seen aligned data: mse / ssim (test_metrics, the
