@@ -15,7 +15,7 @@ import threading
 from pathlib import Path
 
 LIB_PATH = Path(__file__).resolve().parent / "libidn_hip.so"
-ABI_VERSION = 10  # IDN_ABI_VERSION of include/idn.h that SIGNATURES binds
+ABI_VERSION = 11  # IDN_ABI_VERSION of include/idn.h that SIGNATURES binds
 VARIANTS = {"tuning": Path(__file__).resolve().parent / "libidn_hip_tuning.so"}
 
 _c_u8p = ctypes.c_void_p
@@ -66,6 +66,7 @@ SIGNATURES = {
     "idn_quant_u8": (_c_int, [_c_u8p, _c_u8p, _c_u8p, _c_int, _c_int, _c_int, _c_i64, _c_int, _c_u64,
                               _c_u64, _c_vp, _c_vp, _c_vp, _c_vp, _c_size, _c_vp]),
     "idn_quant_workspace_size": (_c_size, [_c_int, _c_int]),
+    "idn_quant_runs_offset": (_c_size, [_c_int, _c_int]),
     "idn_bgr2lab_u8": (_c_int, [_c_u8p, _c_u8p, _c_int, _c_int, _c_int, _c_i64, _c_vp]),
     "idn_lab2bgr_u8": (_c_int, [_c_u8p, _c_u8p, _c_int, _c_int, _c_int, _c_i64, _c_vp]),
     "idn_lbgr2lab_u8": (_c_int, [_c_u8p, _c_u8p, _c_int, _c_int, _c_int, _c_i64, _c_vp]),

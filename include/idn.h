@@ -118,8 +118,10 @@ typedef enum idn_wavelet_mode {
  *      and the wavelet denoiser's options: idn_wavelet_general_workspace_size and
  *      idn_wavelet_denoise_general added, with IDN_WAVELET_DB2 / SYM4 / COIF5 and the enums
  *      idn_wavelet_method and idn_wavelet_mode (no signature changed; the earlier wavelet entry
- *      points reject the new wavelets) */
-#define IDN_ABI_VERSION 10
+ *      points reject the new wavelets)
+ *  11  idn_quant_runs_offset added: where each restart of the quant fit leaves its centres and
+ *      its inertia in the workspace (no signature changed) */
+#define IDN_ABI_VERSION 11
 int idn_abi_version(void);
 const char* idn_version(void);
 const char* idn_last_error(void);
@@ -272,6 +274,14 @@ int idn_quant_u8(const uint8_t* src, uint8_t* dst, uint8_t* labels_out, int n, i
                  const uint64_t* image_ids, const double* centers_in, double* centers_out,
                  void* workspace, size_t ws_bytes, void* stream);
 size_t idn_quant_workspace_size(int n, int k);
+/* diagnostics: byte offset in the workspace, after a device fit, of each restart's result:
+ * run_cen, double [n][3][k][3], every restart's centres (a nonempty cluster's is the exact mean of
+ * its samples, an empty one's the fp32 centre it kept), followed at
+ *   idn_quant_runs_offset(n, k) + round_up(n * 3 * k * 3 * sizeof(double), 256)
+ * by run_inert, double [n][3], the restarts' inertias over the fit's samples.  The centres the
+ * call used are those of the restart with the lowest inertia (the earliest on ties).  A replay
+ * call (centers_in != NULL) leaves both untouched.  tests/quant_fit_model.py restates the fit. */
+size_t idn_quant_runs_offset(int n, int k);
 /* cv2.cvtColor(img, COLOR_BGR2LAB) / (lab, COLOR_LAB2BGR) on 8-bit 3-channel images. */
 int idn_bgr2lab_u8(const uint8_t* src, uint8_t* dst, int n, int h, int w, int64_t row_stride,
                    void* stream);

@@ -195,9 +195,9 @@ def test_abi_workspace_size():
 def test_abi_10_binds_the_new_symbols():
     from idn import _lib as binding
     m = re.search(r"#define\s+IDN_ABI_VERSION\s+(\d+)", (ROOT / "include" / "idn.h").read_text())
-    assert int(m.group(1)) == 10 == binding.ABI_VERSION
+    assert int(m.group(1)) == 11 == binding.ABI_VERSION
     lib = _lib()
-    assert lib.idn_abi_version() == 10
+    assert lib.idn_abi_version() == 11
     for name in ("idn_tv_chambolle_workspace_size", "idn_tv_chambolle_u8"):
         assert name in binding.SIGNATURES
         assert getattr(lib, name).argtypes == binding.SIGNATURES[name][1]
