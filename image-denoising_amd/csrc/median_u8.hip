@@ -563,6 +563,10 @@ static int launch_median(const uint8_t* src, uint8_t* dst, int n, int h, int w, 
   return IDN_OK;
 }
 
+// odd ksize 7..31: the constant-time histogram kernel (median_large_u8.hip)
+int launch_median_large(const uint8_t* src, uint8_t* dst, int n, int h, int w, int c,
+                        int64_t row_stride, int ksize, hipStream_t st);
+
 }  // namespace idn
 
 extern "C" int idn_median_blur_u8(const uint8_t* src, uint8_t* dst, int n, int h, int w, int c,
@@ -572,5 +576,8 @@ extern "C" int idn_median_blur_u8(const uint8_t* src, uint8_t* dst, int n, int h
   if (n == 0) return IDN_OK;
   if (ksize == 3) return launch_median<3>(src, dst, n, h, w, c, row_stride, as_stream(stream));
   if (ksize == 5) return launch_median<5>(src, dst, n, h, w, c, row_stride, as_stream(stream));
-  return set_error(IDN_EUNSUPPORTED, "idn_median_blur_u8: ksize %d not supported (3 or 5)", ksize);
+  if (ksize >= 7 && ksize <= 31 && (ksize & 1))
+    return launch_median_large(src, dst, n, h, w, c, row_stride, ksize, as_stream(stream));
+  return set_error(IDN_EUNSUPPORTED, "idn_median_blur_u8: ksize %d not supported (odd, 3..31)",
+                   ksize);
 }

@@ -6,7 +6,7 @@ the OpenCV / scikit-image calls the reference makes on its preprocessing path:
 
   gaussian_blur(x, ksize)                 cv2.GaussianBlur(x, (ksize, ksize), 0)
   blur(x, ksize=3)                        cv2.blur(x, (ksize, ksize))
-  median_blur(x, ksize)                   cv2.medianBlur(x, ksize)
+  median_blur(x, ksize)                   cv2.medianBlur(x, ksize), odd ksize 3..31
   bilateral_filter(x, d, sc, ss)          cv2.bilateralFilter(x, d, sc, ss, BORDER_CONSTANT)
   random_noise(x, mode, ...)              skimage.util.random_noise (+ U8 cast)
   periodic_pattern / add_pattern          add_periodic_noise's linspace/sin pattern, cv2.add
@@ -34,6 +34,7 @@ from . import _lib
 PIXEL_MEANS = (102.9801, 115.9465, 122.7717)  # lib/model/config.py:252 (BGR)
 
 NOISE_KINDS = {"gaussian": 0, "speckle": 1, "s&p": 2, "sap": 2, "poisson": 3}
+MEDIAN_MAX_KSIZE = 31  # idn_median_blur_u8: odd ksize 3..MEDIAN_MAX_KSIZE
 WAVELETS = {"db1": 0, "haar": 0, "bior1.5": 1, "db2": 2, "sym4": 3, "coif5": 4}  # idn_wavelet
 
 
@@ -90,7 +91,12 @@ def blur(x: torch.Tensor, ksize: int = 3, out: Optional[torch.Tensor] = None) ->
 
 
 def median_blur(x: torch.Tensor, ksize: int = 3, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """cv2.medianBlur(x, ksize); ksize in {3, 5}; bit-exact."""
+    """cv2.medianBlur(x, ksize); odd ksize in 3..MEDIAN_MAX_KSIZE (31); bit-exact.
+
+    The exact per-channel median (rank ksize*ksize // 2) of the ksize x ksize window,
+    BORDER_REPLICATE, images smaller than the window included.  3 and 5 run the sorting-network
+    kernels, 7..31 a histogram kernel whose cost per output grows with ksize, not ksize**2.
+    Any other ksize (even, 1, above 31) raises IdnError."""
     return _filter("idn_median_blur_u8", x, int(ksize), out=out)
 
 

@@ -140,7 +140,9 @@ int idn_gaussian_blur_u8(const uint8_t* src, uint8_t* dst, int n, int h, int w, 
 int idn_box_blur_u8(const uint8_t* src, uint8_t* dst, int n, int h, int w, int c,
                     int64_t row_stride, int ksize, void* stream);
 
-/* cv2.medianBlur(img, ksize), ksize in {3, 5}, BORDER_REPLICATE.
+/* cv2.medianBlur(img, ksize), odd ksize in 3..31, BORDER_REPLICATE: the exact median (rank
+ * ksize*ksize/2) of the window per channel, for any h, w >= 1.  3 and 5 run sorting networks,
+ * 7..31 a per-lane LDS histogram (no workspace).  Any other ksize: IDN_EUNSUPPORTED.
  * Replaces lib/model/test.py:259, lib/roi_data_layer/minibatch.py:1644-1648. Bit-exact. */
 int idn_median_blur_u8(const uint8_t* src, uint8_t* dst, int n, int h, int w, int c,
                        int64_t row_stride, int ksize, void* stream);
