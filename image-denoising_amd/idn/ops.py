@@ -74,6 +74,8 @@ def _filter(fn_name: str, x: torch.Tensor, *args, out: Optional[torch.Tensor] = 
     xb, sq = _u8_batch(x, fn_name)
     n, h, w, c = xb.shape
     y = torch.empty_like(xb) if out is None else out.view(n, h, w, c)
+    if n == 0:  # an empty tensor has no storage: its null data_ptr() is not for the C ABI
+        return _finish(y, sq)
     lib = _lib.load()
     rc = getattr(lib, fn_name)(xb.data_ptr(), y.data_ptr(), n, h, w, c, w * c, *args, _stream())
     _lib.check(rc, fn_name)
