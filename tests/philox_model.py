@@ -10,6 +10,7 @@ right law".  Everything is vectorised over elements; images are the leading axis
     ctr_*(...)                               the counters of each stream
     gauss_u8 / sap / poisson / gauss_f64     skimage.util.random_noise modes on the two streams
     uniform_add / rayleigh_add               the additive noises that are one block's transform
+    gamma_add / brownian_add                 the rejection loop and the four-normal walk
 
 Images are passed as uint8 arrays of shape (n, elems): the flat (y, x, channel) element order of
 each image.  Kinds are idn_noise_kind's numbers.
@@ -102,9 +103,42 @@ def ctr_f64(elems, ids):
     return _ctr(_lo(pr), np.uint64(TAG_F64) ^ (_lo(_hi(pr) << np.uint64(8))), ids)
 
 
-def ctr_add(elems, ids):
-    e = np.arange(elems, dtype=np.uint64)
+def _elems(elems, elems_at=None):
+    """the element indices a model is evaluated on: 0..elems-1, or the chosen ones"""
+    if elems_at is None:
+        return np.arange(elems, dtype=np.uint64)
+    return np.asarray(elems_at, np.uint64).ravel()
+
+
+def ctr_add(elems, ids, elems_at=None):
+    e = _elems(elems, elems_at)
     return _ctr(_lo(e), _hi(e), ids)
+
+
+GAMMA_BOOST = 0xFF      # the attempt number of the boost block (shape < 1)
+GAMMA_ATTEMPTS = 64     # the kernel's attempt cap: attempts 0..63 never reach the boost block
+
+
+def _gamma_c01(e, att):
+    """counter words 0, 1 of element e's attempt att: (e_lo, (e_hi << 8) | att)"""
+    e = np.asarray(e, np.uint64)
+    return _lo(e), _lo(_hi(e) << np.uint64(8)) | np.uint64(att)
+
+
+def ctr_gamma(elems, ids, att, elems_at=None):
+    """gamma: one block per element and attempt; att = GAMMA_BOOST is the boost block"""
+    c0, c1 = _gamma_c01(_elems(elems, elems_at), att)
+    return _ctr(c0, c1, ids)
+
+
+def _brownian_block(e):
+    """the block whose four normals elements 4q..4q+3 take: q = e // 4"""
+    return np.asarray(e, np.uint64) >> np.uint64(2)
+
+
+def ctr_brownian(elems, ids):
+    q = _brownian_block(np.arange(0, elems, 4, dtype=np.uint64))
+    return _ctr(_lo(q), _hi(q), ids)
 
 
 def _words(blocks, elems):
@@ -311,10 +345,11 @@ def gauss_f64(v, seed, ids, kind, mean, var):
 
 
 # ---- additive noises that are a fixed transform of one block -----------------------------------
-def uniform_add(v, seed, ids, high):
-    """out = x + (0 + high * u), u = 53-bit random_sample of words 0 and 1"""
+def uniform_add(v, seed, ids, high, elems_at=None):
+    """out = x + (0 + high * u), u = 53-bit random_sample of words 0 and 1.  elems_at: the element
+    indices the columns of v stand for (default 0..elems-1)."""
     v = np.asarray(v)
-    x, y, _, _ = philox4x32(ctr_add(v.shape[1], ids), add_key(seed, UNIFORM), 10)
+    x, y, _, _ = philox4x32(ctr_add(v.shape[1], ids, elems_at), add_key(seed, UNIFORM), 10)
     bits = ((x >> np.uint64(5)) << np.uint64(26)) | (y >> np.uint64(6))
     u = bits.astype(np.float64) * 2.0 ** -53
     return dict(u=u, f64=_x(v) + (0.0 + float(high) * u))
@@ -330,3 +365,119 @@ def rayleigh_add(v, seed, ids, scale):
     unit = np.sqrt(-2.0 * np.log(uf))
     unit = np.where(uf >= 1.0, 0.0, unit)
     return dict(u=uf, unit=unit, f64=_x(v) + (unit * float(scale) + 0.0))
+
+
+# ---- gamma: Marsaglia-Tsang on one block per attempt ---------------------------------------------
+def _u24(w):
+    """((float)(w >> 8) + 1) * 2^-24 and (float)(w >> 8) * 2^-24 are exact in fp32"""
+    return (w >> np.uint64(8)).astype(np.float64) * 2.0 ** -24
+
+
+def _u_tail(w):
+    """fp32(fp32(w) + 0.5) * 2^-32: two IEEE roundings, then an exact scaling; in (0, 1]"""
+    return (w.astype(np.uint32).astype(np.float32) + np.float32(0.5)).astype(np.float64) * 2.0 ** -32
+
+
+def _pair_normals(wa, wb):
+    """Box-Muller pair of two words: sqrt(-2 ln u1) (cos, sin)(2 pi u2), 24-bit u1 in (0, 1] and
+    u2 in [0, 1), float64"""
+    rad = np.sqrt(-2.0 * np.log(_u24(wa) + 2.0 ** -24))
+    th = 2.0 * np.pi * _u24(wb)
+    return rad * np.cos(th), rad * np.sin(th)
+
+
+def gamma_add(v, seed, ids, scale, shape=1.99, elems_at=None, tau=4e-6):
+    """The kernel's rejection loop, decision for decision, in float64 on the kernel's uniforms.
+    a = fp32(shape) (+ 1 below 1, with boost = u_b^(1/a) from the boost block), d = a - 1/3,
+    c = 1 / sqrt(9 d); attempt t draws z = cos-normal of words 0, 1 and u from word 2 of block
+    (e_lo, (e_hi << 8) | t, id), v1 = 1 + c z, and accepts when v1 > 0 and
+    margin = z^2/2 + d - d v + d ln v - ln u > 0, v = v1^3: g = d v boost.
+
+    Returns a dict of (n, elems) arrays: g, att, z, v1 (of the accepted attempt), boost, ln_ub
+    (ln of the boost uniform, 0 without boost), f64 = x + (g scale + 0), near_at and
+    near = near_at <= tau, plus the scalars a (fp32(shape)), d, c.  near_at is the smallest, over
+    the attempts up to the accepted one, of |v1| / (1 + c |z|) and, where v1 > 0, |margin| / S,
+    S = 1 + z^2/2 + d v + |d ln v| + |ln u|: how close, relative to the size of its terms, the
+    element came to another decision.  alt lists what a near element gives if one such decision
+    falls the other way: rows (flat index, g, z, v1, att) for accepting a near attempt the model
+    rejected, and for the next attempt the model accepts after an accepted near one."""
+    v = np.asarray(v)
+    n, m = v.shape
+    e = _elems(m, elems_at)
+    ids = np.asarray(ids, np.uint64).ravel()
+    k = add_key(seed, GAMMA)
+    size = n * m
+    row, col = np.repeat(np.arange(n), m), np.tile(np.arange(m), n)
+    ee, c2, c3 = e[col], _lo(ids)[row], _hi(ids)[row]
+    a0 = float(np.float32(shape))
+    a = a0
+    boost, ln_ub = np.ones(size), np.zeros(size)
+    if a < 1.0:
+        c0, c1 = _gamma_c01(ee, GAMMA_BOOST)
+        ln_ub = np.log(_u_tail(philox4x32((c0, c1, c2, c3), k, 10)[0]))
+        boost = np.exp(ln_ub / a)
+        a = float(np.float32(a) + np.float32(1.0))
+    d = a - 1.0 / 3.0
+    c = 1.0 / np.sqrt(9.0 * d)
+    out = {name: np.full(size, np.nan) for name in ("g", "z", "v1")}
+    att_of = np.full(size, -1, np.int64)
+    near_at = np.full(size, np.inf)
+    waiting = np.zeros(size, bool)      # accepted at a near attempt: drawn on for alt
+    alt = []
+    live = np.arange(size)
+    for att in range(GAMMA_ATTEMPTS):
+        if live.size == 0:
+            break
+        c0, c1 = _gamma_c01(ee[live], att)
+        w = philox4x32((c0, c1, c2[live], c3[live]), k, 10)
+        z = _pair_normals(w[0], w[1])[0]
+        v1 = 1.0 + c * z
+        pos = v1 > 0.0
+        vv = np.where(pos, v1, 1.0) ** 3
+        ln_u = np.log(_u_tail(w[2]))
+        margin = 0.5 * z * z + d - d * vv + d * np.log(vv) - ln_u
+        s = 1.0 + 0.5 * z * z + d * vv + np.abs(d * np.log(vv)) + np.abs(ln_u)
+        close = np.minimum(np.abs(v1) / (1.0 + c * np.abs(z)),
+                           np.where(pos, np.abs(margin) / s, np.inf))
+        acc = pos & (margin > 0.0)
+        g = d * vv * boost[live]
+        first = ~waiting[live]
+        near_at[live[first]] = np.minimum(near_at[live[first]], close[first])
+        nr = close <= tau
+        for sel in (first & nr & ~acc & pos, ~first & acc):
+            alt += [(int(i), float(gg), float(zz), float(vv1), att)
+                    for i, gg, zz, vv1 in zip(live[sel], g[sel], z[sel], v1[sel])]
+        sel = first & acc
+        out["g"][live[sel]], out["z"][live[sel]], out["v1"][live[sel]] = g[sel], z[sel], v1[sel]
+        att_of[live[sel]] = att
+        waiting[live[sel & nr]] = True
+        live = live[~acc | (sel & nr)]
+    assert (att_of >= 0).all()
+    shp = (n, m)
+    res = {name: val.reshape(shp) for name, val in out.items()}
+    res.update(att=att_of.reshape(shp), boost=boost.reshape(shp), ln_ub=ln_ub.reshape(shp),
+               near_at=near_at.reshape(shp), near=(near_at <= tau).reshape(shp), alt=alt,
+               a=a0, d=d, c=c)
+    res["f64"] = _x(v) + (res["g"] * float(scale) + 0.0)
+    return res
+
+
+# ---- brownian: four normals per block, a sequential walk ------------------------------------------
+def brownian_normals(elems, seed, ids):
+    """(n, elems) float64: element e takes normal e % 4 of block e // 4 -- cos, sin of words 0, 1,
+    then cos, sin of words 2, 3; element 0 is 0 (B_0 = 0)"""
+    x, y, z, w = philox4x32(ctr_brownian(elems, ids), add_key(seed, BROWNIAN), 10)
+    z0, z1 = _pair_normals(x, y)
+    z2, z3 = _pair_normals(z, w)
+    zz = _words([z0, z1, z2, z3], elems).copy()
+    zz[:, 0] = 0.0
+    return zz
+
+
+def brownian_add(v, seed, ids, dt):
+    """Returns dict(z, inc, walk): the normals, the increments sqrt(dt) z and their sequential
+    np.cumsum.  The byte output is a function of the device's own walk (see the GPU test)."""
+    v = np.asarray(v)
+    z = brownian_normals(v.shape[1], seed, ids)
+    inc = np.sqrt(float(dt)) * z
+    return dict(z=z, inc=inc, walk=np.cumsum(inc, axis=1))
