@@ -11,6 +11,8 @@ from .ops import (  # noqa: F401
     gaussian_blur, blur, median_blur, bilateral_filter, random_noise, periodic_pattern,
     add_pattern, periodic_noise, blob, mse, psnr, ssim, nl_means,
     nl_means_colored, denoise_tv_chambolle, estimate_sigma, denoise_wavelet,
+    equalize_hist, clahe, cvt_color_yuv, correct_exposure,
 )
+from . import automold  # noqa: F401
 
 __version__ = "0.1.0"

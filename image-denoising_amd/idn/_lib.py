@@ -106,6 +106,15 @@ SIGNATURES = {
                             _c_vp, _c_size, _c_vp]),
     "idn_ssim_u8": (_c_int, [_c_u8p, _c_u8p, _c_f64p, _c_f64p, _c_f64p, _c_int, _c_int, _c_int, _c_int,
                              _c_i64, _c_i64, _c_int, _c_vp, _c_size, _c_vp]),
+    "idn_bgr2yuv_u8": (_c_int, [_c_u8p, _c_u8p, _c_int, _c_int, _c_int, _c_i64, _c_vp]),
+    "idn_yuv2bgr_u8": (_c_int, [_c_u8p, _c_u8p, _c_int, _c_int, _c_int, _c_i64, _c_vp]),
+    "idn_exposure_workspace_size": (_c_size, [_c_int, _c_int, _c_int, _c_int, _c_int]),
+    "idn_equalize_hist_u8": (_c_int, [_c_u8p, _c_u8p, _c_int, _c_int, _c_int, _c_i64, _c_vp, _c_size,
+                                      _c_vp]),
+    "idn_clahe_u8": (_c_int, [_c_u8p, _c_u8p, _c_int, _c_int, _c_int, _c_i64, _c_dbl, _c_int, _c_int,
+                              _c_vp, _c_size, _c_vp]),
+    "idn_correct_exposure_u8": (_c_int, [_c_u8p, _c_u8p, _c_int, _c_int, _c_int, _c_i64, _c_vp,
+                                         _c_size, _c_vp]),
     "idn_shader_u8": (_c_int, [_c_u8p, _c_u8p, _c_int, _c_int, _c_int, _c_int, _c_i64, _c_dbl, _c_vp]),
     "idn_bloom_u8": (_c_int, [_c_u8p, _c_u8p, _c_int, _c_int, _c_int, _c_int, _c_i64, _c_vp, _c_vp, _c_int,
                               _c_vp, _c_vp]),

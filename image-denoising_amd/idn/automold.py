@@ -9,6 +9,9 @@ reference takes them (same calls, same order), so a seeded `random` gives the re
 parameters.  The filled LINE_8 circles are described by per-radius half-width tables of OpenCV's
 midpoint algorithm (imgproc/drawing.cpp Circle(), fill=1), and the GPU evaluates all 48 blends
 per pixel in one pass (csrc/misc.hip bloom_kernel).
+
+correct_exposure (tools/Automold.py:817-842) is the host-side drop-in of the reference's function
+of that name: ndarrays in, ndarrays out, the work done on the device by idn.ops.correct_exposure.
 """
 from __future__ import annotations
 
@@ -102,3 +105,37 @@ def sun_flare_circles(h: int, w: int, flare_center=(100, 100), angle=-math.pi / 
         circ.append([point[0], point[1], int(rad[i]), *src_color, 1 if i == 0 else 0, 0])
         wts.append([np.float32(alp), np.float32(1 - alp)])
     return np.asarray(circ, np.int32).reshape(-1, 8), np.asarray(wts, np.float32).reshape(-1, 2)
+
+
+# ---- correct_exposure (tools/Automold.py:817-842) ---------------------------------------------------
+
+ERR_NOT_IMAGE = "not a numpy array or list of numpy array"  # Automold.py:141
+
+
+def _is_image(a) -> bool:
+    return isinstance(a, np.ndarray) and a.dtype == np.uint8 and a.ndim == 3 and a.shape[2] == 3
+
+
+def correct_exposure(image, device=None):
+    """Automold.correct_exposure(image): one (H,W,3) uint8 BGR ndarray, or a list of them, through
+    exposure_process on the GPU (idn.ops.correct_exposure); returns an ndarray, or a list in the
+    order given.  Images of the same shape go to the device as one batch."""
+    import torch
+    from . import ops
+    is_list = isinstance(image, list)
+    images = image if is_list else [image]
+    if not all(isinstance(a, np.ndarray) for a in images):
+        raise Exception(ERR_NOT_IMAGE)  # Automold.py verify_image
+    if not all(_is_image(a) for a in images):
+        raise ValueError("correct_exposure: images must be (H,W,3) uint8 BGR arrays")
+    device = torch.device("cuda") if device is None else device
+    out = [None] * len(images)
+    by_shape: dict = {}
+    for i, a in enumerate(images):
+        by_shape.setdefault(a.shape, []).append(i)
+    for idx in by_shape.values():
+        batch = torch.from_numpy(np.stack([images[i] for i in idx])).to(device)
+        res = ops.correct_exposure(batch).cpu().numpy()
+        for k, i in enumerate(idx):
+            out[i] = res[k]
+    return out if is_list else out[0]

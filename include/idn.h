@@ -39,8 +39,9 @@
  *     IDN_EINVAL); idn_noise_ycc_u8 (2-byte u8 pointers, 16-byte out_f64, IDN_EUNSUPPORTED: use
  *     idn_noise_u8); idn_gaussian_blob_f32 fuses only a source at 0 mod 8 with a blob at 0 mod
  *     16 (IDN_EUNSUPPORTED otherwise: idn_gaussian_blur_u8 + idn_blob_f32 give the same blob);
- *     the workspaces of idn_mse_u8, idn_ssim_u8, idn_tv_chambolle_u8 and idn_estimate_sigma are
- *     8-byte aligned (IDN_EINVAL).  The other workspaces are taken from the base of a device allocation.
+ *     the workspaces of idn_mse_u8, idn_ssim_u8, idn_tv_chambolle_u8, idn_estimate_sigma,
+ *     idn_equalize_hist_u8, idn_clahe_u8 and idn_correct_exposure_u8 are 8-byte aligned
+ *     (IDN_EINVAL).  The other workspaces are taken from the base of a device allocation.
  *   - Return IDN_OK (0) or a negative idn_status; idn_last_error() returns a thread-local
  *     message for the last failing call on the calling thread.
  *
@@ -120,7 +121,9 @@ typedef enum idn_wavelet_mode {
  *      idn_wavelet_method and idn_wavelet_mode (no signature changed; the earlier wavelet entry
  *      points reject the new wavelets)
  *  11  idn_quant_runs_offset added: where each restart of the quant fit leaves its centres and
- *      its inertia in the workspace (no signature changed) */
+ *      its inertia in the workspace (no signature changed); later, under the same number,
+ *      exposure correction: idn_bgr2yuv_u8, idn_yuv2bgr_u8, idn_equalize_hist_u8, idn_clahe_u8,
+ *      idn_exposure_workspace_size and idn_correct_exposure_u8 added (no signature changed) */
 #define IDN_ABI_VERSION 11
 int idn_abi_version(void);
 const char* idn_version(void);
@@ -543,6 +546,65 @@ int idn_ssim_u8(const uint8_t* a, const uint8_t* b, double* ssim_out, double* ss
                 double* mse_out, int n, int h, int w, int c, int64_t row_stride_a,
                 int64_t row_stride_b, int win_size, void* workspace, size_t workspace_bytes,
                 void* stream);
+
+/* ---- exposure correction (Automold correct_exposure: tools/Automold.py:817-842) -------------- */
+
+/* OpenCV 3.4's 8-bit code as recalled; cv2 is not available to the tests, so parity with cv2
+ * itself is unpinned and the numpy model tests/exposure_model.py, written from the text below,
+ * defines the result.  The kernels are bit-equal to it, and an image gives the same bytes alone
+ * and in any batch: all that crosses workgroups is integer atomic addition.
+ * descale(v) = (v + 8192) >> 14 (arithmetic), sat clips to 0..255, rne rounds an fp32 value half to
+ * even.
+ *
+ * idn_bgr2yuv_u8 (COLOR_BGR2YUV, c = 3):  Y = descale(1868 B + 9617 G + 4899 R),
+ *   U = sat(descale((B - Y) 8061 + (128 << 14))),  V = sat(descale((R - Y) 14369 + (128 << 14))).
+ * idn_yuv2bgr_u8 (COLOR_YUV2BGR, c = 3):  u = U - 128, v = V - 128,  B = sat(Y + descale(33292 u)),
+ *   G = sat(Y + descale(-6472 u - 9519 v)),  R = sat(Y + descale(18678 v)).  The round trip is
+ *   not the identity.
+ * idn_equalize_hist_u8 (cv2.equalizeHist per image, c = 1): with hist over the image and i0 its
+ *   first non-zero bin, a constant image comes back; otherwise scale = 255.f / (h w - hist[i0]),
+ *   lut[i0] = 0 and lut[i] = sat(rne((float)sum(hist[i0+1 .. i]) scale)).
+ * idn_clahe_u8 (cv2.createCLAHE(clip_limit, (tiles_x, tiles_y)).apply per image, c = 1):
+ *   if tiles_x divides w and tiles_y divides h the tiles cut the image; otherwise the image is
+ *   extended by BORDER_REFLECT_101, by tiles_y - h % tiles_y rows at the bottom and
+ *   tiles_x - w % tiles_x columns at the right, BOTH whenever either fails to divide (a dimension
+ *   that divides then grows by a whole tiles_y or tiles_x).  Per tile of area pixels:
+ *   clip = clip_limit == 0 ? 0 : max((int)(clip_limit area / 256), 1); if clip > 0 the bins are
+ *   cut at clip, every bin gains excess / 256, and bins 0, step, 2 step, ... gain one more while
+ *   r = excess % 256 lasts (step = max(256 / r, 1)); lut[i] = sat(rne((float)cumsum[i] 255.f /
+ *   area)).  Each pixel blends the tables of the four nearest tile centres bilinearly in fp32:
+ *   txf = x (1.f / tile_w) - 0.5f, tx1 = floor(txf), xa = txf - tx1, tx2 = min(tx1 + 1, tiles_x -
+ *   1), tx1 = max(tx1, 0), the same in y, out = sat(rne((L11 (1 - xa) + L12 xa)(1 - ya) +
+ *   (L21 (1 - xa) + L22 xa) ya)), every product and sum rounded to fp32.
+ *   tiles_x, tiles_y in 1..16, h > tiles_y and w > tiles_x (one reflection is enough),
+ *   clip_limit >= 0 and finite (0: no clipping).
+ * idn_correct_exposure_u8 (c = 3, BGR): the tone part of exposure_process: BGR -> YUV, Y <-
+ *   (17 Y) / 20 where Y > 150 (trunc(0.85 Y) for every byte), CLAHE(2.0, (4, 4)), equalizeHist,
+ *   CLAHE(2.0, (4, 4)), YUV -> BGR with the source's U and V.  Byte for byte the composition of the
+ *   entry points above, in seven launches that store no YUV image (csrc/exposure.hip).  It does NOT
+ *   run exposure_process's last step, fastNlMeansDenoisingColored(., 3, 3, 7, 21): the caller (the
+ *   binding idn.ops.correct_exposure) runs idn_nlmeans_colored_u8 on the result.  h, w > 4.
+ * workspace: idn_exposure_workspace_size(n, h, w, tiles_x, tiles_y) bytes, 8-byte aligned;
+ *   (1, 1) for idn_equalize_hist_u8, (4, 4) for idn_correct_exposure_u8; 0 for n, h or w < 1 or a
+ *   grid outside 1..16.  Histograms (u32), tables and one byte plane of luma.
+ * IDN_EINVAL: null image pointer, src == dst, n < 0, h or w < 1, row_stride < w*c, a parameter
+ *   outside the ranges above, workspace not 8-byte aligned.  IDN_EWORKSPACE: workspace missing or
+ *   too small.  IDN_EUNSUPPORTED: an image of 2^31 pixels or more.  n == 0 returns IDN_OK without
+ *   a launch.  Every argument check runs before any HIP call. */
+int idn_bgr2yuv_u8(const uint8_t* src, uint8_t* dst, int n, int h, int w, int64_t row_stride,
+                   void* stream);
+int idn_yuv2bgr_u8(const uint8_t* src, uint8_t* dst, int n, int h, int w, int64_t row_stride,
+                   void* stream);
+size_t idn_exposure_workspace_size(int n, int h, int w, int tiles_x, int tiles_y);
+int idn_equalize_hist_u8(const uint8_t* src, uint8_t* dst, int n, int h, int w,
+                         int64_t row_stride, void* workspace, size_t workspace_bytes,
+                         void* stream);
+int idn_clahe_u8(const uint8_t* src, uint8_t* dst, int n, int h, int w, int64_t row_stride,
+                 double clip_limit, int tiles_x, int tiles_y, void* workspace,
+                 size_t workspace_bytes, void* stream);
+int idn_correct_exposure_u8(const uint8_t* src, uint8_t* dst, int n, int h, int w,
+                            int64_t row_stride, void* workspace, size_t workspace_bytes,
+                            void* stream);
 
 /* ---- shader / bloom noise types ---------------------------------------------------------- */
 
