@@ -11,7 +11,7 @@ from .ops import (  # noqa: F401
     gaussian_blur, blur, median_blur, bilateral_filter, random_noise, periodic_pattern,
     add_pattern, periodic_noise, blob, mse, psnr, ssim, nl_means,
     nl_means_colored, denoise_tv_chambolle, estimate_sigma, denoise_wavelet,
-    equalize_hist, clahe, cvt_color_yuv, correct_exposure,
+    equalize_hist, clahe, cvt_color_yuv, correct_exposure, wiener,
 )
 from . import automold  # noqa: F401
 

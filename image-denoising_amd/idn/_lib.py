@@ -101,6 +101,10 @@ SIGNATURES = {
     "idn_estimate_sigma_workspace_size": (_c_size, [_c_int, _c_int, _c_int, _c_int, _c_int]),
     "idn_estimate_sigma": (_c_int, [_c_u8p, _c_f64p, _c_f64p, _c_int, _c_int, _c_int, _c_int, _c_i64,
                                     _c_vp, _c_size, _c_vp]),
+    "idn_wiener_workspace_size": (_c_size, [_c_int, _c_int]),
+    "idn_wiener_u8": (_c_int, [_c_u8p, _c_u8p, _c_f64p, _c_int, _c_int, _c_int, _c_int, _c_i64,
+                               _c_int, _c_int, _c_int, _c_f64p, _c_i64, _c_f64p, _c_vp, _c_size,
+                               _c_vp]),
     "idn_metrics_workspace_size": (_c_size, [_c_int, _c_int, _c_int, _c_int, _c_int]),
     "idn_mse_u8": (_c_int, [_c_u8p, _c_u8p, _c_f64p, _c_int, _c_int, _c_int, _c_int, _c_i64, _c_i64,
                             _c_vp, _c_size, _c_vp]),

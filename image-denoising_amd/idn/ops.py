@@ -17,6 +17,7 @@ the OpenCV / scikit-image calls the reference makes on its preprocessing path:
   nl_means_colored(x, h, h_color, t, s)   cv2.fastNlMeansDenoisingColored(x, None, h, h_color, t, s)
   denoise_tv_chambolle(x, weight, eps, n) skimage.restoration.denoise_tv_chambolle (0.14.2)
   estimate_sigma(x, average_sigmas)       skimage.restoration.estimate_sigma (multichannel=True)
+  wiener(x, ksize, noise, border=...)     scipy.signal.wiener per channel plane (1.15.3)
   equalize_hist(x)                        cv2.equalizeHist(x)
   clahe(x, clip_limit, tile_grid)         cv2.createCLAHE(clip_limit, tile_grid).apply(x)
   cvt_color_yuv(x, to_yuv)                cv2.cvtColor(x, COLOR_BGR2YUV / COLOR_YUV2BGR)
@@ -1167,6 +1168,139 @@ def estimate_sigma(x: torch.Tensor, average_sigmas: bool = False) -> torch.Tenso
         else:
             out = out[:, 0]
     return _finish(out, sq)
+
+
+# ---- adaptive Wiener filter ----------------------------------------------------------------------
+
+WIENER_MAX_KSIZE = 31                              # idn_wiener_u8: odd window sides 1..31
+WIENER_BORDERS = {"zero": 0, "reflect101": 1}      # idn_wiener_border
+WIENER_TILE = (128, 256)  # output rows x interleaved byte columns (W*C) of one workgroup
+
+
+def _wiener_check(x, ksize, noise, border, out, out_u8):
+    """argument errors of wiener, raised before the device is looked at; returns (kh, kw)"""
+    name = "wiener"
+    if not isinstance(x, torch.Tensor):
+        raise TypeError(f"{name}: expected a torch.Tensor, got {type(x).__name__}")
+    if x.dtype != torch.uint8:
+        raise TypeError(f"{name}: expected uint8 images, got {x.dtype}")
+    if x.dim() not in (3, 4):
+        raise ValueError(f"{name}: expected (H,W,C) or (N,H,W,C), got shape {tuple(x.shape)}")
+    c = x.shape[-1]
+    if c not in (1, 3):
+        raise ValueError(f"{name}: 1 or 3 channels supported, got {c}")
+    h, w = x.shape[-3], x.shape[-2]
+    if h < 1 or w < 1:
+        raise ValueError(f"{name}: empty image {h} x {w}")
+    ks = (ksize, ksize) if isinstance(ksize, numbers.Integral) else ksize
+    try:
+        kh, kw = ks
+        ok = all(isinstance(k, numbers.Integral) and 1 <= k <= WIENER_MAX_KSIZE and k % 2 == 1
+                 for k in (kh, kw))
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"{name}: ksize must be an odd integer in 1..{WIENER_MAX_KSIZE} or a "
+                         f"pair (kh, kw) of them, got {ksize!r}")
+    kh, kw = int(kh), int(kw)
+    if border not in WIENER_BORDERS:
+        raise ValueError(f"{name}: border must be one of {sorted(WIENER_BORDERS)}, got {border!r}")
+    if border == "reflect101" and (kh // 2 >= h or kw // 2 >= w):
+        raise ValueError(f"{name}: border='reflect101' needs kh//2 < H and kw//2 < W "
+                         f"(window {kh} x {kw}, image {h} x {w})")
+    if out not in ("u8", "f64"):
+        raise ValueError(f"{name}: out must be 'u8' or 'f64', got {out!r}")
+    if out_u8 is not None:
+        if out != "u8":
+            raise ValueError(f"{name}: out_u8 given with out={out!r}")
+        if (not isinstance(out_u8, torch.Tensor) or out_u8.dtype != torch.uint8
+                or out_u8.shape != x.shape or out_u8.device != x.device):
+            raise ValueError(f"{name}: out_u8 must be a uint8 tensor shaped like x on x's device")
+    n = x.shape[0] if x.dim() == 4 else 1
+    if isinstance(noise, torch.Tensor):
+        if noise.dtype != torch.float64:
+            raise TypeError(f"{name}: a noise tensor must be float64, got {noise.dtype}")
+        if noise.device != x.device:
+            raise ValueError(f"{name}: a noise tensor must be on x's device ({x.device}), "
+                             f"got {noise.device}")
+        if tuple(noise.shape) not in ((c,), (n, c)):
+            raise ValueError(f"{name}: a noise tensor must have shape ({c},) or ({n}, {c}), "
+                             f"got {tuple(noise.shape)}")
+    elif noise is not None:
+        if isinstance(noise, (str, bytes)):
+            raise TypeError(f"{name}: noise must be None, a number, {c} numbers or a tensor")
+        try:
+            vals = np.asarray(noise, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise TypeError(f"{name}: noise must be None, a number, {c} numbers or a tensor, "
+                            f"got {type(noise).__name__}") from None
+        if vals.shape not in ((), (c,)):
+            raise ValueError(f"{name}: noise must be one number or {c} (one per channel), "
+                             f"got shape {vals.shape}")
+        if not (np.isfinite(vals).all() and (vals >= 0).all()):
+            raise ValueError(f"{name}: noise must be finite and not negative, got {noise!r}")
+    if x.device.type != "cuda":
+        raise ValueError(f"{name}: idn runs on the GPU only; got a {x.device} tensor "
+                         "(move it with .cuda(); there is no CPU fallback)")
+    return kh, kw
+
+
+def wiener(x: torch.Tensor, ksize=3, noise=None, *, border: str = "zero", out: str = "u8",
+           out_u8: Optional[torch.Tensor] = None, return_noise: bool = False):
+    """scipy.signal.wiener(x[i][..., ch].astype(float64), (kh, kw), noise) on every channel plane
+    of uint8 images, (N,)H,W,C with C 1 or 3: the adaptive local-statistics (Lee, Matlab wiener2)
+    filter.  With the window's mean m and variance v (exact: integer sums, divided once),
+    r = m where v < noise, else (x - m) * (1 - noise / v) + m: flat regions are averaged, edges
+    and texture are kept.  ksize: an odd int or (kh, kw), each 1..31; the cost does not grow with
+    the window's area.
+    noise, on the 0..255 scale squared (estimate_sigma(x) ** 2 is that scale): None estimates it
+    per (image, channel) as scipy does, the mean of v over the plane, which counts the signal and
+    so overestimates on structured images; a float; C floats; or a float64 device tensor (C,) or
+    (N, C), which is not validated (host values must be finite and not negative).
+    border: 'zero' is scipy's (taps outside the image are 0, which dims the rim), 'reflect101'
+    mirrors the image (cv2's default border; needs kh//2 < H and kw//2 < W).
+    out: 'u8' (clip(rint(r), 0, 255), round half to even) | 'f64' (r).  Where v == 0 the result is
+    m; scipy gives NaN there when noise is 0 as well (an all-zero image with noise=None).
+    return_noise=True also returns the float64 (N, C) device tensor ((C,) for one image) of the
+    noise used.  Bit-equal to the numpy model tests/wiener_model.py, which tests/golden/wiener.npz
+    pins to scipy 1.15.3; the same bits on every call and in every batch.  x may be contiguous or
+    have padded rows; out_u8, if given, must then share x's layout."""
+    kh, kw = _wiener_check(x, ksize, noise, border, out, out_u8)
+    name = "wiener"
+    if out == "u8":
+        xb, y8, pitch, sq = _nlm_layout(name, x, out_u8)
+    else:
+        xb, sq = _as_batch(x, name)
+        y8, pitch = None, _row_pitch(xb)
+        if pitch is None:
+            xb = xb.contiguous()
+            pitch = xb.shape[2] * xb.shape[3]
+    n, h, w, c = xb.shape
+    y64 = torch.empty((n, h, w, c), dtype=torch.float64, device=xb.device) if out == "f64" else None
+    nz, nz_stride = None, 0
+    if isinstance(noise, torch.Tensor):
+        nz = noise.contiguous()
+        nz_stride = c if nz.dim() == 2 else 0
+    elif noise is not None:
+        vals = np.array(np.broadcast_to(np.asarray(noise, dtype=np.float64), (c,)))
+        nz = torch.from_numpy(vals).to(xb.device)
+    used = torch.empty((n, c), dtype=torch.float64, device=xb.device) if return_noise else None
+    if n > 0:
+        lib = _lib.load()
+        nbytes = lib.idn_wiener_workspace_size(n, c) if nz is None else 0
+        ws = _workspace(nbytes, xb.device) if nbytes else None
+        rc = lib.idn_wiener_u8(xb.data_ptr(), y8.data_ptr() if y8 is not None else None,
+                               y64.data_ptr() if y64 is not None else None, n, h, w, c, pitch,
+                               kh, kw, WIENER_BORDERS[border],
+                               nz.data_ptr() if nz is not None else None, nz_stride,
+                               used.data_ptr() if used is not None else None,
+                               ws.data_ptr() if ws is not None else None, nbytes, _stream())
+        _lib.check(rc, "idn_wiener_u8")
+    if out == "u8":
+        res = out_u8 if out_u8 is not None else _finish(y8, sq)
+    else:
+        res = _finish(y64, sq)
+    return (res, _finish(used, sq)) if return_noise else res
 
 
 # ---- quality metrics ---------------------------------------------------------------------------

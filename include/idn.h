@@ -123,7 +123,9 @@ typedef enum idn_wavelet_mode {
  *  11  idn_quant_runs_offset added: where each restart of the quant fit leaves its centres and
  *      its inertia in the workspace (no signature changed); later, under the same number,
  *      exposure correction: idn_bgr2yuv_u8, idn_yuv2bgr_u8, idn_equalize_hist_u8, idn_clahe_u8,
- *      idn_exposure_workspace_size and idn_correct_exposure_u8 added (no signature changed) */
+ *      idn_exposure_workspace_size and idn_correct_exposure_u8 added (no signature changed);
+ *      later, under the same number, the adaptive Wiener filter: idn_wiener_workspace_size and
+ *      idn_wiener_u8 added, with the enum idn_wiener_border (no signature changed) */
 #define IDN_ABI_VERSION 11
 int idn_abi_version(void);
 const char* idn_version(void);
@@ -515,6 +517,51 @@ size_t idn_estimate_sigma_workspace_size(int n, int h, int w, int c, int is_f64)
 int idn_estimate_sigma(const uint8_t* src_u8, const double* src_f64, double* dst, int n, int h,
                        int w, int c, int64_t row_stride, void* workspace, size_t ws_bytes,
                        void* stream);
+
+/* ---- wiener (scipy.signal.wiener per channel plane: the adaptive local-statistics filter) ---- */
+
+/* Not a reference interface: the adaptive linear denoiser of the bank (Lee / Matlab wiener2),
+ * the natural consumer of idn_estimate_sigma's number, squared.  Every channel plane of every
+ * image is filtered on its own, as scipy.signal.wiener(plane.astype(float64), (kh, kw), noise).
+ * With S1 = sum t and S2 = sum t^2 over the kh x kw window of a sample x, as integers, and
+ * n = kh*kw:
+ *   m = double(S1) / n,  v = double(S2) / n - m*m  (the product rounds, then the difference),
+ *   r = v == 0 ? m : (v < noise ? m : (x - m) * (1 - noise / v) + m).
+ * border: IDN_WIENER_ZERO takes a tap outside the image as 0 (scipy's correlate 'same'; it dims
+ * the rim), IDN_WIENER_REFLECT101 as the mirrored sample (cv2's default border, numpy's
+ * pad mode 'reflect'; needs kh/2 < h and kw/2 < w).  kh, kw: odd, 1..31, each on its own.
+ * noise: device array on the 0..255 scale squared, read at noise[i*noise_image_stride + ch]
+ * (noise_image_stride c, or 0 when one row of c values serves every image), not validated; NULL
+ * estimates it per (image, channel) as scipy does, the mean of v over the plane, here as
+ * double(Q) / double(n*n*h*w) with the exact integer Q = sum (n*S2 - S1*S1): within 3.3e-16
+ * relative of scipy's mean, which rounds per sample.  On a structured image that mean counts
+ * the signal and overestimates.  noise_out (nullable): the n*c values used.
+ * v == 0 returns m: the one departure from scipy, which gives NaN there when noise is 0 too
+ * (an all-zero image with no noise given).
+ * dst_f64 (n*h*w*c doubles, compact) receives r, dst_u8 (src's layout) clip(rint(r), 0, 255),
+ * round half to even; either may be NULL, not both.  tests/wiener_model.py is the definition and
+ * tests/golden/wiener.npz pins it to scipy 1.15.3; both outputs are bit-equal to the model, the
+ * same bits on every call and in every batch.  The cost per sample does not grow with kh*kw:
+ * running column sums and at most about 20 LDS reads (wide windows are summed in two levels).
+ * Given noise: one launch, the image read once and written once.  noise NULL: a first pass forms Q with integer atomics and the filter pass recomputes
+ * the sums.  Stream-ordered and capture-safe: no allocation, host copy or synchronisation.
+ * workspace: idn_wiener_workspace_size(n, c) bytes (8 per (image, channel); 0 for n <= 0 or c not
+ *   1 or 3), 8-byte aligned, needed only when noise is NULL.
+ * IDN_EINVAL: null src, both destinations null, dst_u8 == src, n < 0, h or w < 1, c not 1 or 3,
+ *   row_stride < w*c, kh or kw even or outside 1..31, unknown border, reflect101 with kh/2 >= h
+ *   or kw/2 >= w, a double pointer not 8-byte aligned, noise_image_stride neither 0 nor c.
+ *   IDN_EWORKSPACE: noise NULL and the workspace missing or too small.  IDN_EUNSUPPORTED: noise
+ *   NULL and h*w above 2^28 (Q would leave 64 bits).  n == 0 returns IDN_OK without a launch.
+ *   Every argument check runs before any HIP call. */
+typedef enum idn_wiener_border {
+  IDN_WIENER_ZERO = 0,
+  IDN_WIENER_REFLECT101 = 1
+} idn_wiener_border;
+size_t idn_wiener_workspace_size(int n, int c);
+int idn_wiener_u8(const uint8_t* src, uint8_t* dst_u8, double* dst_f64, int n, int h, int w, int c,
+                  int64_t row_stride, int kh, int kw, int border, const double* noise,
+                  int64_t noise_image_stride, double* noise_out, void* workspace, size_t ws_bytes,
+                  void* stream);
 
 /* ---- quality metrics (skimage 0.14.2 measure.compare_mse / compare_psnr / compare_ssim) ---- */
 
