@@ -1110,30 +1110,50 @@ int check_filter_args(const uint8_t* src, uint8_t* dst, int n, int h, int w, int
 
 }  // namespace idn
 
+// 3 and 5 with the window's own sigma, and the 3 box, run the kernels above; every other odd
+// window up to 31 and every given sigma the kernels of blur_large_u8.hip
+static int gaussian_blur_any(const uint8_t* src, uint8_t* dst, int n, int h, int w, int c,
+                             int64_t row_stride, int ksize, double sigma, void* stream,
+                             const char* name) {
+  using namespace idn;
+  if (int e = check_filter_args(src, dst, n, h, w, c, row_stride, name)) return e;
+  uint16_t taps[32];
+  if (int e = gaussian_taps(ksize, sigma, taps, name)) return e;
+  if (n == 0) return IDN_OK;
+  if (ksize == 3 && sigma == 0.0)
+    return launch_stencil<OP_GAUSS3>(src, dst, n, h, w, c, row_stride, as_stream(stream), name);
+  if (ksize == 5 && sigma == 0.0)
+    return launch_stencil<OP_GAUSS5>(src, dst, n, h, w, c, row_stride, as_stream(stream), name);
+  return launch_gauss_large(src, dst, n, h, w, c, row_stride, ksize, taps, as_stream(stream),
+                            name);
+}
+
 extern "C" int idn_gaussian_blur_u8(const uint8_t* src, uint8_t* dst, int n, int h, int w, int c,
                                     int64_t row_stride, int ksize, void* stream) {
-  using namespace idn;
-  if (int e = check_filter_args(src, dst, n, h, w, c, row_stride, "idn_gaussian_blur_u8")) return e;
-  if (n == 0) return IDN_OK;
-  if (ksize == 3)
-    return launch_stencil<OP_GAUSS3>(src, dst, n, h, w, c, row_stride, as_stream(stream),
-                                     "idn_gaussian_blur_u8");
-  if (ksize == 5)
-    return launch_stencil<OP_GAUSS5>(src, dst, n, h, w, c, row_stride, as_stream(stream),
-                                     "idn_gaussian_blur_u8");
-  return set_error(IDN_EUNSUPPORTED, "idn_gaussian_blur_u8: ksize %d not supported (3 or 5)",
-                   ksize);
+  return gaussian_blur_any(src, dst, n, h, w, c, row_stride, ksize, 0.0, stream,
+                           "idn_gaussian_blur_u8");
+}
+
+extern "C" int idn_gaussian_blur_sigma_u8(const uint8_t* src, uint8_t* dst, int n, int h, int w,
+                                          int c, int64_t row_stride, int ksize, double sigma,
+                                          void* stream) {
+  return gaussian_blur_any(src, dst, n, h, w, c, row_stride, ksize, sigma, stream,
+                           "idn_gaussian_blur_sigma_u8");
 }
 
 extern "C" int idn_box_blur_u8(const uint8_t* src, uint8_t* dst, int n, int h, int w, int c,
                                int64_t row_stride, int ksize, void* stream) {
   using namespace idn;
   if (int e = check_filter_args(src, dst, n, h, w, c, row_stride, "idn_box_blur_u8")) return e;
+  if (ksize < 3 || ksize > 31 || !(ksize & 1))
+    return set_error(IDN_EUNSUPPORTED, "idn_box_blur_u8: ksize %d not supported (odd, 3..31)",
+                     ksize);
   if (n == 0) return IDN_OK;
   if (ksize == 3)
     return launch_stencil<OP_BOX3>(src, dst, n, h, w, c, row_stride, as_stream(stream),
                                    "idn_box_blur_u8");
-  return set_error(IDN_EUNSUPPORTED, "idn_box_blur_u8: ksize %d not supported (3)", ksize);
+  return launch_box_large(src, dst, n, h, w, c, row_stride, ksize, as_stream(stream),
+                          "idn_box_blur_u8");
 }
 
 extern "C" int idn_gaussian_blur_f64(const double* src, double* dst, int n, int h, int w, int c,
@@ -1170,7 +1190,9 @@ extern "C" int idn_gaussian_blob_f32(const uint8_t* src, float* blob, int n, int
                                 "idn_gaussian_blob_f32")) return e;
   if (n == 0) return IDN_OK;
   const int64_t rb = (int64_t)w * c;
-  IDN_CHECK_ARG(ksize == 3 || ksize == 5, "idn_gaussian_blob_f32: ksize must be 3 or 5");
+  if (ksize >= 7 && ksize <= 31 && (ksize & 1))  // the caller composes the blur and idn_blob_f32
+    return set_error(IDN_EUNSUPPORTED, "idn_gaussian_blob_f32: ksize %d is not fused", ksize);
+  IDN_CHECK_ARG(ksize == 3 || ksize == 5, "idn_gaussian_blob_f32: ksize must be odd, 3..31");
   if (!(stripe_ok(c, rb, row_stride, h, src, blob) && row_stride == rb && rb <= TILE_RBMAX &&
         h > ksize && ((uintptr_t)blob & 15) == 0))
     return set_error(IDN_EUNSUPPORTED, "idn_gaussian_blob_f32: layout not fused");

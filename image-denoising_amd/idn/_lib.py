@@ -33,6 +33,8 @@ SIGNATURES = {
     "idn_version": (ctypes.c_char_p, []),
     "idn_last_error": (ctypes.c_char_p, []),
     "idn_gaussian_blur_u8": (_c_int, [_c_u8p, _c_u8p, _c_int, _c_int, _c_int, _c_int, _c_i64, _c_int, _c_vp]),
+    "idn_gaussian_blur_sigma_u8": (_c_int, [_c_u8p, _c_u8p, _c_int, _c_int, _c_int, _c_int, _c_i64, _c_int, _c_dbl, _c_vp]),
+    "idn_gaussian_taps": (_c_int, [_c_int, _c_dbl, _c_vp]),
     "idn_box_blur_u8": (_c_int, [_c_u8p, _c_u8p, _c_int, _c_int, _c_int, _c_int, _c_i64, _c_int, _c_vp]),
     "idn_median_blur_u8": (_c_int, [_c_u8p, _c_u8p, _c_int, _c_int, _c_int, _c_int, _c_i64, _c_int, _c_vp]),
     "idn_bilateral_u8": (_c_int, [_c_u8p, _c_u8p, _c_int, _c_int, _c_int, _c_int, _c_i64, _c_int, _c_dbl, _c_dbl, _c_vp]),

@@ -125,7 +125,10 @@ typedef enum idn_wavelet_mode {
  *      exposure correction: idn_bgr2yuv_u8, idn_yuv2bgr_u8, idn_equalize_hist_u8, idn_clahe_u8,
  *      idn_exposure_workspace_size and idn_correct_exposure_u8 added (no signature changed);
  *      later, under the same number, the adaptive Wiener filter: idn_wiener_workspace_size and
- *      idn_wiener_u8 added, with the enum idn_wiener_border (no signature changed) */
+ *      idn_wiener_u8 added, with the enum idn_wiener_border (no signature changed); later, under
+ *      the same number, the wide smoothers: idn_gaussian_taps and idn_gaussian_blur_sigma_u8
+ *      added, idn_gaussian_blur_u8 and idn_box_blur_u8 accept every odd ksize 3..31 (no
+ *      signature changed) */
 #define IDN_ABI_VERSION 11
 int idn_abi_version(void);
 const char* idn_version(void);
@@ -135,13 +138,41 @@ const char* idn_last_error(void);
 
 /* ---- denoising filters (u8 -> u8, src != dst) ------------------------------------------ */
 
-/* cv2.GaussianBlur(img, (ksize, ksize), 0), ksize in {3, 5}, BORDER_REFLECT_101.
- * Replaces e.g. lib/model/test.py:224, lib/roi_data_layer/minibatch.py:1636-1639. Bit-exact. */
+/* The Gaussian smoother, odd ksize in 3..31, BORDER_REFLECT_101 (repeated, so images smaller than
+ * the radius are legal): Q8 taps t[0..ksize-1] that sum to 256 (idn_gaussian_taps) and
+ *   dst = (sum_i sum_j t[i] t[j] src[y+i-r, x+j-r] + 32768) >> 16.
+ * At 3, 5 and 7 this is cv2.GaussianBlur(img, (ksize, ksize), 0) bit for bit (the dyadic kernels);
+ * 3 and 5 replace e.g. lib/model/test.py:224, lib/roi_data_layer/minibatch.py:1636-1639 and run the
+ * stencil kernels.  Beyond the dyadic kernels tests/blur_model.py is the definition and parity
+ * with cv2 is unpinned: OpenCV rounds the taps the same way but, as far as is known, does not
+ * renormalise them to 256 (its sum at 29 would be 252 and darken a flat 255 to 247); here a
+ * constant image always comes back unchanged.  7..31 run a separable LDS kernel whose cost grows
+ * with ksize, not ksize^2: measured on an MI355X, 256 x 600x1000x3, 1.01 / 1.06 / 1.41 / 1.62 /
+ * 2.11 ms at 7 / 9 / 15 / 21 / 31 (the copy of the batch: 0.165 ms; 5 on the stencil kernel:
+ * 0.166 ms).  Any other ksize: IDN_EUNSUPPORTED. */
 int idn_gaussian_blur_u8(const uint8_t* src, uint8_t* dst, int n, int h, int w, int c,
                          int64_t row_stride, int ksize, void* stream);
 
-/* cv2.blur(img, (ksize, ksize)), ksize = 3, BORDER_REFLECT_101.
- * Replaces lib/model/test.py:241,1767, lib/roi_data_layer/minibatch.py:1640-1643. Bit-exact. */
+/* The same with a given sigma (cv2.GaussianBlur(img, (ksize, ksize), sigma) up to the caveat
+ * above).  sigma = 0 is idn_gaussian_blur_u8; a negative, NaN or infinite sigma: IDN_EINVAL.
+ * Only (3, 0) and (5, 0) run the stencil kernels. */
+int idn_gaussian_blur_sigma_u8(const uint8_t* src, uint8_t* dst, int n, int h, int w, int c,
+                               int64_t row_stride, int ksize, double sigma, void* stream);
+
+/* Host only, no HIP call: the ksize Q8 taps the two entries above use.  sigma = 0 at 3, 5, 7:
+ * [64,128,64], [16,64,96,64,16], [8,28,56,72,56,28,8].  Otherwise s = sigma, or
+ * 0.3*((ksize-1)*0.5 - 1) + 0.8 for sigma = 0; g[i] = exp(-(i - ksize/2)^2 / (2 s^2)) in double,
+ * t[i] = rint(256 g[i] / sum g), and 256 - sum t is added to the centre tap.  A tap can be 0
+ * (the outer ones at 29 and 31) or 256 (the identity, e.g. (3, 0.1)). */
+int idn_gaussian_taps(int ksize, double sigma, uint16_t* taps);
+
+/* cv2.blur(img, (ksize, ksize)), odd ksize in 3..31, BORDER_REFLECT_101 (repeated): with S the
+ * window's sum, dst = (2 S + ksize^2) / (2 ksize^2); ksize^2 is odd, so S / ksize^2 is never a
+ * tie and this is cv2's result under either rounding.  Bit-exact.  3 replaces
+ * lib/model/test.py:241,1767, lib/roi_data_layer/minibatch.py:1640-1643 and runs the stencil
+ * kernel; 5..31 run running column sums whose cost does not grow with the window's area: measured
+ * on an MI355X, 256 x 600x1000x3, 1.12 / 1.25 / 1.48 / 1.70 ms at 5 / 7 / 15 / 31 (idn_wiener_u8
+ * with the noise given, same run: 1.29 / 1.35 / 1.54 / 1.79).  Any other ksize: IDN_EUNSUPPORTED. */
 int idn_box_blur_u8(const uint8_t* src, uint8_t* dst, int n, int h, int w, int c,
                     int64_t row_stride, int ksize, void* stream);
 
@@ -308,7 +339,8 @@ int idn_lab2lbgr_u8(const uint8_t* src, uint8_t* dst, int n, int h, int w, int64
 /* cv2.GaussianBlur(img, (ksize, ksize), 0) then prep_im_for_blob at scale 1.0
  * (lib/utils/blob.py:33-47): blob = float32(float64(v) - mean[ch]), dense (n, h, w, c) float32
  * written by the filter kernel (the filtered u8 image never reaches HBM).  mean: host double[3].
- * IDN_EUNSUPPORTED unless C = 3 and compact rows of 8k <= 3024 bytes. */
+ * IDN_EUNSUPPORTED unless C = 3, ksize 3 or 5 and compact rows of 8k <= 3024 bytes (compose
+ * idn_gaussian_blur_u8 and idn_blob_f32 then). */
 int idn_gaussian_blob_f32(const uint8_t* src, float* blob, int n, int h, int w, int c,
                           int64_t row_stride, int ksize, const double* mean, void* stream);
 
