@@ -14,7 +14,7 @@
 // Brownian's cumulative sum runs as a three-pass scan (per-block sums, per-image block offsets,
 // per-element prefix), fp64 throughout; its summation order differs from np.cumsum's strictly
 // sequential one by rounding only.
-#include "idn_common.hpp"
+#include "noise_common.hpp"
 
 #include <math.h>
 
@@ -41,8 +41,6 @@ struct AddArgs {
 __device__ __forceinline__ uint64_t image_id(const AddArgs& a, int img) {
   return a.ids ? a.ids[img] : a.offset + (uint64_t)img;
 }
-
-__device__ __forceinline__ double img_as_float_(uint32_t v) { return __dmul_rn((double)v, 1.0 / 255.0); }
 
 // (y).astype(np.uint8) for float64 y: (uint8)(int32)trunc(y); out of int32 range or NaN -> 0
 __device__ __forceinline__ uint32_t u8_wrap(double y) {
@@ -127,7 +125,7 @@ __global__ __launch_bounds__(256) void noise_add_kernel(AddArgs a) {
     const int64_t flat = (int64_t)img * a.elems + e;
     const double u = unit_draw<KIND>(a, img, e, flat);
     const int64_t boff = elem_offset(a, img, e);
-    const double out = __dadd_rn(img_as_float_(a.src[boff]), noise_of<KIND>(a, u));
+    const double out = __dadd_rn(img_as_float(a.src[boff]), noise_of<KIND>(a, u));
     if (a.out_f64) a.out_f64[flat] = out;
     if (a.out_u8) a.out_u8[boff] = (uint8_t)u8_wrap(__dmul_rn(255.0, out));
   }
@@ -262,11 +260,9 @@ static int noise_add_impl(const uint8_t* src, uint8_t* out_u8, double* out_f64, 
                           int w, int c, int64_t row_stride, int kind, double p0, double p1,
                           uint64_t seed, uint64_t offset, const uint64_t* ids,
                           const double* replay, void* workspace, size_t ws_bytes, void* stream) {
-  IDN_CHECK_ARG(src, "idn_noise_add_u8: null src");
-  IDN_CHECK_ARG(out_u8 || out_f64, "idn_noise_add_u8: at least one of out_u8 / out_f64 is required");
-  IDN_CHECK_ARG(n >= 0 && h > 0 && w > 0 && c >= 1 && c <= 4, "idn_noise_add_u8: bad shape");
-  IDN_CHECK_ARG(n <= 65535, "idn_noise_add_u8: at most 65535 images per call");
-  IDN_CHECK_ARG(row_stride >= (int64_t)w * c, "idn_noise_add_u8: row_stride < w*c");
+  const int rc = check_noise_shape("idn_noise_add_u8", src, out_u8, out_f64, n, h, w, c,
+                                   row_stride, false);
+  if (rc != IDN_OK) return rc;
   IDN_CHECK_ARG(kind >= IDN_NOISE_UNIFORM && kind <= IDN_NOISE_BROWNIAN,
                 "idn_noise_add_u8: unknown kind %d", kind);
   if (n == 0) return IDN_OK;

@@ -1,6 +1,7 @@
-// Per-element noise arithmetic of the u8 noise kernels (noise.hip), on the Philox streams described
-// there: skimage.util.random_noise's apply followed by the caller's U8 cast (255 * out).astype(
-// uint8).  Two Gaussian streams:
+// Per-element noise arithmetic of the u8 noise kernels (noise.hip; img_as_float / clip01 / u8_of
+// also serve noise_poisson.hip and noise_add.hip), on the Philox streams described in noise.hip:
+// skimage.util.random_noise's apply followed by the caller's U8 cast (255 * out).astype(uint8).
+// Two Gaussian streams:
 //   * u8-only outputs (the denoise branches' input): 16-bit uniforms, fp32 Box-Muller, the U8
 //     cast computed on the 0..255 scale in fp32 -- floor(clip(v + 255 n)) / floor(clip(v + v n))
 //     -- which differs from numpy's float64 apply + cast only where 255 * out lies within ~3e-4 of

@@ -171,6 +171,61 @@ def _ids_tensor(image_ids, n: int, device) -> torch.Tensor:
     return t.to(device).contiguous()
 
 
+def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
+    return t.data_ptr() if t is not None else None
+
+
+def _noise_kind(mode: str, mean, var, amount, salt_vs_pepper):
+    """random_noise's mode -> (kind, p0, p1) of idn_noise_u8"""
+    kind = NOISE_KINDS.get(mode.lower())
+    if kind is None:
+        raise ValueError(f"random_noise: unsupported mode {mode!r}; supported: {sorted(NOISE_KINDS)}")
+    if kind in (0, 1):
+        return kind, float(mean), float(var)
+    if kind == 2:
+        return kind, float(amount), float(salt_vs_pepper)
+    return kind, 0.0, 0.0
+
+
+def _noise_outputs(name: str, xb: torch.Tensor, out: str, out_u8: Optional[torch.Tensor]):
+    """out = 'u8' / 'f64' / 'both' -> (y8, y64), each a batch shaped like xb or None"""
+    want_u8 = out in ("u8", "both")
+    want_f64 = out in ("f64", "both")
+    if not (want_u8 or want_f64):
+        raise ValueError(f"{name}: out must be 'u8', 'f64' or 'both'")
+    y8 = (out_u8.view(xb.shape) if out_u8 is not None else _empty_like_img(xb, torch.uint8)) if want_u8 else None
+    y64 = _empty_like_img(xb, torch.float64) if want_f64 else None
+    return y8, y64
+
+
+def _noise_result(out: str, y8, y64, squeeze: bool):
+    if out == "u8":
+        return _finish(y8, squeeze)
+    if out == "f64":
+        return _finish(y64, squeeze)
+    return _finish(y8, squeeze), _finish(y64, squeeze)
+
+
+def _replay_field(replay, xb: torch.Tensor, need: int, bad: str, bad_count: Optional[str] = None):
+    """the replayed random field, contiguous: float64 on xb's device with `need` elements (the
+    messages are the caller's; bad_count may name {got} and {need})"""
+    if replay is None:
+        return None
+    if replay.device != xb.device or replay.dtype != torch.float64:
+        raise ValueError(bad)
+    if replay.numel() != need:
+        raise ValueError((bad_count or bad).format(got=replay.numel(), need=need))
+    return replay.contiguous()
+
+
+def _stream_ids(name: str, image_ids, replay, n: int, device) -> Optional[torch.Tensor]:
+    if image_ids is None:
+        return None
+    if replay is not None:
+        raise ValueError(f"{name}: image_ids applies to the Philox stream, not to replay")
+    return _ids_tensor(image_ids, n, device)
+
+
 def random_noise(x: torch.Tensor, mode: str = "gaussian", *, mean: float = 0.0, var: float = 0.01,
                  amount: float = 0.05, salt_vs_pepper: float = 0.5, seed: int = 0,
                  offset: int = 0, replay: Optional[torch.Tensor] = None, out: str = "u8",
@@ -193,58 +248,26 @@ def random_noise(x: torch.Tensor, mode: str = "gaussian", *, mean: float = 0.0, 
     if slots is not None:
         return _random_noise_slots(x, mode, mean, var, amount, salt_vs_pepper, seed, out, out_u8,
                                    image_ids, slots)
-    kind = NOISE_KINDS.get(mode.lower())
-    if kind is None:
-        raise ValueError(f"random_noise: unsupported mode {mode!r}; supported: {sorted(NOISE_KINDS)}")
+    kind, p0, p1 = _noise_kind(mode, mean, var, amount, salt_vs_pepper)
     xb, sq = _u8_batch(x, "random_noise")
     n, h, w, c = xb.shape
-    want_u8 = out in ("u8", "both")
-    want_f64 = out in ("f64", "both")
-    if not (want_u8 or want_f64):
-        raise ValueError("random_noise: out must be 'u8', 'f64' or 'both'")
-    y8 = (out_u8.view(n, h, w, c) if out_u8 is not None else _empty_like_img(xb, torch.uint8)) if want_u8 else None
-    y64 = _empty_like_img(xb, torch.float64) if want_f64 else None
-    if kind in (0, 1):
-        p0, p1 = float(mean), float(var)
-    elif kind == 2:
-        p0, p1 = float(amount), float(salt_vs_pepper)
-    else:
-        p0 = p1 = 0.0
-    rp = None
-    if replay is not None:
-        rp = replay
-        if rp.device != xb.device or rp.dtype != torch.float64:
-            raise ValueError("random_noise: replay must be a float64 tensor on the same device")
-        need = (2 if kind == 2 else 1) * xb.numel()
-        if rp.numel() != need:
-            raise ValueError(f"random_noise: replay has {rp.numel()} elements, expected {need}")
-        rp = rp.contiguous()
+    y8, y64 = _noise_outputs("random_noise", xb, out, out_u8)
+    rp = _replay_field(replay, xb, (2 if kind == 2 else 1) * xb.numel(),
+                       "random_noise: replay must be a float64 tensor on the same device",
+                       "random_noise: replay has {got} elements, expected {need}")
     lib = _lib.load()
-    ws = None
     ws_bytes = lib.idn_noise_workspace_size(kind, n)
-    if ws_bytes:
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=xb.device)
-    if image_ids is not None:
-        if rp is not None:
-            raise ValueError("random_noise: image_ids applies to the Philox stream, not to replay")
-        ids = _ids_tensor(image_ids, n, xb.device)
-        rc = lib.idn_noise_ids_u8(xb.data_ptr(), y8.data_ptr() if y8 is not None else None,
-                                  y64.data_ptr() if y64 is not None else None, n, h, w, c, w * c,
-                                  kind, p0, p1, int(seed) & (2 ** 64 - 1), ids.data_ptr(),
-                                  ws.data_ptr() if ws is not None else None, ws_bytes, _stream())
+    ws = _workspace(ws_bytes, xb.device) if ws_bytes else None
+    ids = _stream_ids("random_noise", image_ids, rp, n, xb.device)
+    head = (xb.data_ptr(), _ptr(y8), _ptr(y64), n, h, w, c, w * c, kind, p0, p1,
+            int(seed) & (2 ** 64 - 1))
+    if ids is not None:
+        rc = lib.idn_noise_ids_u8(*head, ids.data_ptr(), _ptr(ws), ws_bytes, _stream())
         _lib.check(rc, "idn_noise_ids_u8")
     else:
-        rc = lib.idn_noise_u8(xb.data_ptr(), y8.data_ptr() if y8 is not None else None,
-                              y64.data_ptr() if y64 is not None else None, n, h, w, c, w * c,
-                              kind, p0, p1, int(seed) & (2 ** 64 - 1), int(offset),
-                              rp.data_ptr() if rp is not None else None,
-                              ws.data_ptr() if ws is not None else None, ws_bytes, _stream())
+        rc = lib.idn_noise_u8(*head, int(offset), _ptr(rp), _ptr(ws), ws_bytes, _stream())
         _lib.check(rc, "idn_noise_u8")
-    if out == "u8":
-        return _finish(y8, sq)
-    if out == "f64":
-        return _finish(y64, sq)
-    return _finish(y8, sq), _finish(y64, sq)
+    return _noise_result(out, y8, y64, sq)
 
 
 def ycc_fusable(x: torch.Tensor) -> bool:
@@ -273,20 +296,12 @@ def random_noise_ycc(x: torch.Tensor, mode: str = "gaussian", *, mean: float = 0
     xb = xb.contiguous()
     y64 = _empty_like_img(xb, torch.float64)
     keys = torch.empty((n, 6), dtype=torch.int64, device=xb.device)
-    rp = None
-    if replay is not None:
-        if replay.device != xb.device or replay.dtype != torch.float64 or replay.numel() != xb.numel():
-            raise ValueError("random_noise_ycc: replay must be a float64 field of x's shape on its device")
-        rp = replay.contiguous()
-    ids = None
-    if image_ids is not None:
-        if rp is not None:
-            raise ValueError("random_noise_ycc: image_ids applies to the Philox stream, not to replay")
-        ids = _ids_tensor(image_ids, n, xb.device)
+    rp = _replay_field(replay, xb, xb.numel(),
+                       "random_noise_ycc: replay must be a float64 field of x's shape on its device")
+    ids = _stream_ids("random_noise_ycc", image_ids, rp, n, xb.device)
     rc = _lib.load().idn_noise_ycc_u8(xb.data_ptr(), None, y64.data_ptr(), n, h, w, kind,
                                       float(mean), float(var), int(seed) & (2 ** 64 - 1),
-                                      int(offset), ids.data_ptr() if ids is not None else None,
-                                      rp.data_ptr() if rp is not None else None, keys.data_ptr(),
+                                      int(offset), _ptr(ids), _ptr(rp), keys.data_ptr(),
                                       _stream())
     _lib.check(rc, "idn_noise_ycc_u8")
     return _finish(y64, sq), keys
@@ -303,9 +318,7 @@ def _slots_tensor(slots, device) -> torch.Tensor:
 
 def _random_noise_slots(x, mode, mean, var, amount, salt_vs_pepper, seed, out, out_u8, image_ids,
                         slots):
-    kind = NOISE_KINDS.get(mode.lower())
-    if kind is None:
-        raise ValueError(f"random_noise: unsupported mode {mode!r}; supported: {sorted(NOISE_KINDS)}")
+    kind, p0, p1 = _noise_kind(mode, mean, var, amount, salt_vs_pepper)
     if out != "u8" or out_u8 is None or image_ids is None:
         raise ValueError("random_noise: slots needs out='u8', out_u8 and image_ids")
     xb, _ = _u8_batch(x, "random_noise")
@@ -319,18 +332,12 @@ def _random_noise_slots(x, mode, mean, var, amount, salt_vs_pepper, seed, out, o
     sl = _slots_tensor(slots, xb.device)
     n = sl.numel()
     ids = _ids_tensor(image_ids, n, xb.device)
-    if kind in (0, 1):
-        p0, p1 = float(mean), float(var)
-    elif kind == 2:
-        p0, p1 = float(amount), float(salt_vs_pepper)
-    else:
-        p0 = p1 = 0.0
     lib = _lib.load()
     ws_bytes = lib.idn_noise_workspace_size(kind, n)
     ws = _workspace(ws_bytes, xb.device) if ws_bytes else None
     rc = lib.idn_noise_slots_u8(xb.data_ptr(), y8.data_ptr(), None, n, h, w, c, w * c, kind, p0, p1,
                                 int(seed) & (2 ** 64 - 1), ids.data_ptr(), sl.data_ptr(),
-                                ws.data_ptr() if ws is not None else None, ws_bytes, _stream())
+                                _ptr(ws), ws_bytes, _stream())
     _lib.check(rc, "idn_noise_slots_u8")
     return out_u8
 
@@ -357,43 +364,23 @@ def noise_add(x: torch.Tensor, mode: str, level: float, *, seed: int = 0, offset
         raise ValueError(f"noise_add: unsupported mode {mode!r}; supported: {sorted(ADD_NOISE_KINDS)}")
     xb, sq = _u8_batch(x, "noise_add")
     n, h, w, c = xb.shape
-    want_u8 = out in ("u8", "both")
-    want_f64 = out in ("f64", "both")
-    if not (want_u8 or want_f64):
-        raise ValueError("noise_add: out must be 'u8', 'f64' or 'both'")
-    y8 = (out_u8.view(n, h, w, c) if out_u8 is not None else _empty_like_img(xb, torch.uint8)) if want_u8 else None
-    y64 = _empty_like_img(xb, torch.float64) if want_f64 else None
+    y8, y64 = _noise_outputs("noise_add", xb, out, out_u8)
     p0, p1 = (float(shape), float(level)) if kind == 5 else (float(level), 0.0)
-    rp = None
-    if replay is not None:
-        if replay.device != xb.device or replay.dtype != torch.float64 or replay.numel() != xb.numel():
-            raise ValueError("noise_add: replay must be float64, on the same device, one value per element")
-        rp = replay.contiguous()
+    rp = _replay_field(replay, xb, xb.numel(),
+                       "noise_add: replay must be float64, on the same device, one value per element")
     lib = _lib.load()
     ws_bytes = lib.idn_noise_add_workspace_size(kind, n, h, w, c)
     ws = _workspace(ws_bytes, xb.device) if ws_bytes else None
-    if image_ids is not None:
-        if rp is not None:
-            raise ValueError("noise_add: image_ids applies to the Philox stream, not to replay")
-        ids = _ids_tensor(image_ids, n, xb.device)
-        rc = lib.idn_noise_add_ids_u8(xb.data_ptr(), y8.data_ptr() if y8 is not None else None,
-                                      y64.data_ptr() if y64 is not None else None, n, h, w, c,
-                                      w * c, kind, p0, p1, int(seed) & (2 ** 64 - 1),
-                                      ids.data_ptr(), ws.data_ptr() if ws is not None else None,
-                                      ws_bytes, _stream())
+    ids = _stream_ids("noise_add", image_ids, rp, n, xb.device)
+    head = (xb.data_ptr(), _ptr(y8), _ptr(y64), n, h, w, c, w * c, kind, p0, p1,
+            int(seed) & (2 ** 64 - 1))
+    if ids is not None:
+        rc = lib.idn_noise_add_ids_u8(*head, ids.data_ptr(), _ptr(ws), ws_bytes, _stream())
         _lib.check(rc, "idn_noise_add_ids_u8")
     else:
-        rc = lib.idn_noise_add_u8(xb.data_ptr(), y8.data_ptr() if y8 is not None else None,
-                                  y64.data_ptr() if y64 is not None else None, n, h, w, c, w * c,
-                                  kind, p0, p1, int(seed) & (2 ** 64 - 1), int(offset),
-                                  rp.data_ptr() if rp is not None else None,
-                                  ws.data_ptr() if ws is not None else None, ws_bytes, _stream())
+        rc = lib.idn_noise_add_u8(*head, int(offset), _ptr(rp), _ptr(ws), ws_bytes, _stream())
         _lib.check(rc, "idn_noise_add_u8")
-    if out == "u8":
-        return _finish(y8, sq)
-    if out == "f64":
-        return _finish(y64, sq)
-    return _finish(y8, sq), _finish(y64, sq)
+    return _noise_result(out, y8, y64, sq)
 
 
 _PATTERN_CACHE: dict = {}

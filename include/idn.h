@@ -16,7 +16,8 @@
  *     documented exceptions).  The RNG position is explicit: Philox4x32 keyed by (seed ^ a per-
  *     mode tag), counter = (element group, stream tag, image id) with image id = offset + i (or
  *     an explicit id array), so results do not depend on how a batch is split across launches,
- *     ranks or memory layouts.  Streams (csrc/noise.hip, noise_apply.hpp):
+ *     ranks or memory layouts.  Streams (csrc/noise.hip, noise_poisson.hip,
+ *     noise_apply.hpp):
  *       gaussian / speckle, u8-only output  Philox4x32-7, one block per 8 elements: 16-bit
  *         uniforms, fp32 Box-Muller (the extreme radius cell refined to 32 bits from a second
  *         block, |z| <= 6.66), U8 computed as floor(clip(v + 255 n)) / floor(clip(v + v n)) in

@@ -1,4 +1,5 @@
-"""Exact host model of the Philox noise streams (csrc/noise.hip, noise_apply.hpp, noise_add.hip).
+"""Exact host model of the Philox noise streams (csrc/noise.hip, noise_poisson.hip, noise_apply.hpp,
+noise_add.hip).
 
 numpy only: the definition of the streams restated from the documented counter layout, keys and
 integer mappings, so a test can ask "equal to the reference, draw for draw" instead of "has the

@@ -27,10 +27,10 @@ a knob):
                                                    blob(gaussian_blur(x))
   noise.hip flat (src & 15, out_u8 & 15)           test_random_noise_u8[*-8x16] at every offset but
                                                    (0,0): noise_elem16_kernel, noise_poisson_kernel
-  noise.hip poisson compact (src & 15)             test_random_noise_u8[poisson-8x16] at (8,*) (4,4)
+  noise_poisson.hip compact (src & 15)             test_random_noise_u8[poisson-8x16] at (8,*) (4,4)
                                                    (1,0) (3,5): unique_mask_kernel
   noise.hip ycc form (src & 1, out_f64 & 15)       test_noise_ycc_rejects_misaligned: IDN_EUNSUPPORTED
-  noise.hip add_pattern / copy_slots (& 15)        test_add_pattern, test_periodic_noise,
+  noise_pattern.hip add_pattern / copy_slots (& 15) test_add_pattern, test_periodic_noise,
                                                    test_copy_slots at every offset but (0,0)
   quant.hip flat (src | dst | labels & 15)         test_quantize at every offset but (0,0,0)
   wavelet.hip wl_color_minmax flat (src & 3)       test_wavelet[db1-L2-12x20-u8, bior1.5-40x64-u8]
