@@ -8,7 +8,8 @@ lib/utils/blob.py), computed by hand-written HIP kernels for gfx950 behind a C-A
 from ._lib import IdnError, LIB_PATH  # noqa: F401
 from . import ops  # noqa: F401
 from .ops import (  # noqa: F401
-    gaussian_blur, blur, median_blur, bilateral_filter, random_noise, periodic_pattern,
+    gaussian_blur, blur, median_blur, adaptive_median, bilateral_filter, random_noise,
+    periodic_pattern,
     add_pattern, periodic_noise, blob, mse, psnr, ssim, nl_means,
     nl_means_colored, denoise_tv_chambolle, estimate_sigma, denoise_wavelet,
     equalize_hist, clahe, cvt_color_yuv, correct_exposure, wiener,

@@ -7,6 +7,7 @@ the OpenCV / scikit-image calls the reference makes on its preprocessing path:
   gaussian_blur(x, ksize, sigma=0)        cv2.GaussianBlur(x, (ksize, ksize), sigma), odd 3..31
   blur(x, ksize=3)                        cv2.blur(x, (ksize, ksize)), odd ksize 3..31
   median_blur(x, ksize)                   cv2.medianBlur(x, ksize), odd ksize 3..31
+  adaptive_median(x, max_ksize)           the window-growing median (Gonzalez & Woods §5.3)
   bilateral_filter(x, d, sc, ss)          cv2.bilateralFilter(x, d, sc, ss, BORDER_CONSTANT)
   random_noise(x, mode, ...)              skimage.util.random_noise (+ U8 cast)
   periodic_pattern / add_pattern          add_periodic_noise's linspace/sin pattern, cv2.add
@@ -40,6 +41,7 @@ PIXEL_MEANS = (102.9801, 115.9465, 122.7717)  # lib/model/config.py:252 (BGR)
 
 NOISE_KINDS = {"gaussian": 0, "speckle": 1, "s&p": 2, "sap": 2, "poisson": 3}
 MEDIAN_MAX_KSIZE = 31  # idn_median_blur_u8: odd ksize 3..MEDIAN_MAX_KSIZE
+ADAPTIVE_MEDIAN_MAX_KSIZE = 31  # idn_adaptive_median_u8: odd max_ksize 3..31
 BLUR_MAX_KSIZE = 31    # idn_gaussian_blur_u8 / idn_box_blur_u8: odd ksize 3..BLUR_MAX_KSIZE
 # strip rows x byte columns (W*C) of one workgroup of the wide kernels: the box, and the Gaussian
 # by channel count (whole groups of 4 pixels)
@@ -139,6 +141,35 @@ def median_blur(x: torch.Tensor, ksize: int = 3, out: Optional[torch.Tensor] = N
     kernels, 7..31 a histogram kernel whose cost per output grows with ksize, not ksize**2.
     Any other ksize (even, 1, above 31) raises IdnError."""
     return _filter("idn_median_blur_u8", x, int(ksize), out=out)
+
+
+def adaptive_median(x: torch.Tensor, max_ksize: int = 15, out: Optional[torch.Tensor] = None, *,
+                    return_ksize: bool = False):
+    """The adaptive median filter for salt & pepper (Hwang & Haddad 1995; Gonzalez & Woods §5.3).
+
+    Per channel plane, BORDER_REPLICATE, images smaller than the window included; for a sample z
+        for k = 3, 5, .., max_ksize:  mn, mx, md = min, max, median of the k x k window
+            if mn < md < mx:  out = z if mn < z < mx else md;  ksize = k;  stop
+        no k passed:  out = md of the max_ksize window;  ksize = 0
+    (the fall-through rule of the 3rd and later editions of Gonzalez & Woods; the 2nd outputs z).
+    max_ksize, odd in 3..ADAPTIVE_MEDIAN_MAX_KSIZE (31), is a cap on the window, not a strength:
+    the window grows only where the impulses are dense, and a clean sample comes back unchanged.
+    Bit-equal to tests/adaptive_median_model.py.  return_ksize=True returns (y, ksize) with the
+    uint8 map of x's shape of the level that decided each sample (0: the fall-through).
+    Any other max_ksize (even, 1, above 31, negative) raises IdnError."""
+    fn_name = "idn_adaptive_median_u8"
+    xb, sq = _u8_batch(x, fn_name)
+    n, h, w, c = xb.shape
+    y = torch.empty_like(xb) if out is None else out.view(n, h, w, c)
+    km = torch.empty_like(xb) if return_ksize else None
+    if n != 0:  # an empty tensor has no storage: its null data_ptr() is not for the C ABI
+        rc = _lib.load().idn_adaptive_median_u8(
+            xb.data_ptr(), y.data_ptr(), None if km is None else km.data_ptr(), n, h, w, c, w * c,
+            int(max_ksize), _stream())
+        _lib.check(rc, fn_name)
+    if return_ksize:
+        return _finish(y, sq), _finish(km, sq)
+    return _finish(y, sq)
 
 
 def bilateral_filter(x: torch.Tensor, d: int = 9, sigma_color: float = 20.0,

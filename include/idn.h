@@ -129,6 +129,8 @@ typedef enum idn_wavelet_mode {
  *      idn_wiener_u8 added, with the enum idn_wiener_border (no signature changed); later, under
  *      the same number, the wide smoothers: idn_gaussian_taps and idn_gaussian_blur_sigma_u8
  *      added, idn_gaussian_blur_u8 and idn_box_blur_u8 accept every odd ksize 3..31 (no
+ *      signature changed); later,
+ *      under the same number, the adaptive median filter: idn_adaptive_median_u8 added (no
  *      signature changed) */
 #define IDN_ABI_VERSION 11
 int idn_abi_version(void);
@@ -183,6 +185,28 @@ int idn_box_blur_u8(const uint8_t* src, uint8_t* dst, int n, int h, int w, int c
  * Replaces lib/model/test.py:259, lib/roi_data_layer/minibatch.py:1644-1648. Bit-exact. */
 int idn_median_blur_u8(const uint8_t* src, uint8_t* dst, int n, int h, int w, int c,
                        int64_t row_stride, int ksize, void* stream);
+
+/* The adaptive median filter for salt & pepper (Hwang & Haddad 1995; Gonzalez & Woods, "Digital
+ * Image Processing", section 5.3), per channel plane of every image, BORDER_REPLICATE, any
+ * h, w >= 1 (replicated samples count with their multiplicity).  K = max_ksize is odd, in 3..31.
+ * For a sample z at (y, x):
+ *   for k = 3, 5, ..., K:
+ *     mn, mx = min, max of the k x k window;  md = its median (rank k*k/2 of the sorted window)
+ *     if mn < md < mx:                      stage A: the median is not an extreme
+ *       dst = (mn < z < mx) ? z : md        stage B, with the mn / mx of this same k
+ *       ksize = k;  stop
+ *   if no k passed:  dst = md of the K x K window;  ksize = 0
+ * The fall-through (no level passes) outputs the median at K, the rule of the 3rd and later
+ * editions of Gonzalez & Woods (the 2nd edition outputs z there).  A constant image comes back
+ * unchanged with ksize 0 everywhere.  There is no parameter other than K, which caps the window
+ * and is no strength: the window grows only where the impulses are dense.
+ * ksize_map (nullable) receives ksize per sample, 3..K or 0, in dst's layout with the same
+ * row_stride.  No workspace, one launch; any pointer alignment and any row_stride >= w*c, padding
+ * bytes of dst and ksize_map are never written.  Bit-equal to tests/adaptive_median_model.py.
+ * Any other max_ksize (even, 1, above 31, negative): IDN_EUNSUPPORTED, before any HIP call. */
+int idn_adaptive_median_u8(const uint8_t* src, uint8_t* dst, uint8_t* ksize_map /* nullable */,
+                           int n, int h, int w, int c, int64_t row_stride, int max_ksize,
+                           void* stream);
 
 /* cv2.bilateralFilter(img, d, sigma_color, sigma_space, borderType=BORDER_CONSTANT), c = 3
  * (or 1).  Replaces lib/model/test.py:278, lib/roi_data_layer/minibatch.py:1658-1663.
