@@ -162,6 +162,29 @@ def test_product_library_holds_no_tuning_only_wavelet_kernels():
         assert name not in prod, name
 
 
+def test_product_library_holds_no_tuning_only_stencil_kernels():
+    """The stencil's A/B forms live in the tuning library alone: the kernel handles of the pitched
+    tile's identity probe (OP = 3) and of the flat tile with nontemporal stores (NTS = 1) are
+    exported by libidn_hip_tuning.so and not by libidn_hip.so"""
+    import subprocess
+    from idn import _lib
+    tuning = Path(_lib.VARIANTS["tuning"])
+    assert tuning.exists(), "libidn_hip_tuning.so not built: __graft_entry__.build() builds both"
+    nm = "/opt/rocm/lib/llvm/bin/llvm-nm"
+    if not Path(nm).exists():
+        nm = "nm"
+
+    def defined(p):
+        return subprocess.run([nm, "-D", "--defined-only", str(p)], capture_output=True, text=True,
+                              check=True).stdout
+
+    prod, tun = defined(_lib_path()), defined(tuning)
+    assert "stencil_u8_ptILi3ELi1ELi9ELi1ELi2ELi2ELi0E" in prod  # the headline kernel
+    for name in ("stencil_u8_ptILi3ELi3E", "stencil_u8_ldsILi3ELi1ELi6ELi0ELi1ELi0E"):
+        assert name in tun, name
+        assert name not in prod, name
+
+
 def test_abi_version_matches_header_and_binding():
     """IDN_ABI_VERSION (include/idn.h) == idn_abi_version() of the built library == the version
     idn/_lib.py binds; the binding refuses a library of another version"""

@@ -19,7 +19,7 @@ a knob):
   -----------------------------------------------  ------------------------------------------------
   stripe.hpp stripe_ok (src & 7, dst & 7)          test_filter[*-13x104 ..1400] at (4,4) (1,0) (0,1)
                                                    (3,5): stencil_u8_generic / median_u8_generic
-  stencil_u8.hip tile_dma_ok (src & 15): the flat  test_filter[gaussian*/box3-19x1008, 19x928] at
+  stencil_tile.hip tile_dma_ok (src & 15): the flat test_filter[gaussian*/box3-19x1008, 19x928] at
     tile's LDS-DMA fetch                           (8,8) (8,0): register fetch, `full` branch; the
                                                    DMA side itself at (0,0) (0,8)
   stencil_u8.hip idn_gaussian_blob_f32 (blob & 15) test_gaussian_blob[*] at (8,8) (0,8) (4,4) (0,4):

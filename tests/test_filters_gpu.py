@@ -212,7 +212,9 @@ def test_stencil_forms_agree(dev, layout, shape):
 
 @pytest.mark.parametrize("w,pad", [(1000, 8), (344, 16), (1400, 0)])
 def test_stencil_row_stride_and_wide_rows(dev, w, pad):
-    """row_stride > W*C (strided rows take the stripe form) and rows wider than the LDS tile"""
+    """row_stride > W*C (strided rows take the stripe form) and rows wider than the LDS tile: the
+    Gaussians and the 3x3 box (width 1400 is five segments, the long bands; the others the burst
+    form)"""
     import torch
     import idn
     import oracle
@@ -224,13 +226,15 @@ def test_stencil_row_stride_and_wide_rows(dev, w, pad):
     rs = (rs + 7) // 8 * 8
     buf = torch.zeros((2, 41, rs), dtype=torch.uint8, device="cuda")
     buf[:, :, : w * 3] = torch.from_numpy(img.reshape(2, 41, w * 3)).cuda()
-    out = torch.full_like(buf, 77)
-    for k in (3, 5):
-        rc = lib.idn_gaussian_blur_u8(buf.data_ptr(), out.data_ptr(), 2, 41, w, 3, rs, k, None)
+    for fn, k, ref in ((lib.idn_gaussian_blur_u8, 3, oracle.cv.gaussian_blur),
+                       (lib.idn_gaussian_blur_u8, 5, oracle.cv.gaussian_blur),
+                       (lib.idn_box_blur_u8, 3, oracle.cv.blur)):
+        out = torch.full_like(buf, 77)
+        rc = fn(buf.data_ptr(), out.data_ptr(), 2, 41, w, 3, rs, k, None)
         assert rc == 0
         torch.cuda.synchronize()
         got = out[:, :, : w * 3].cpu().numpy().reshape(2, 41, w, 3)
-        assert np.array_equal(got, oracle.cv.gaussian_blur(img, k)), k
+        assert np.array_equal(got, ref(img, k)), (fn.__name__, k)
         assert bool((out[:, :, w * 3:] == 77).all())  # padding untouched
 
 

@@ -3,7 +3,10 @@
 environment knobs, interleaved rounds in ONE process, median kernel time via HIP events.  Each
 variant's output is compared with the first variant's (the knobs must not change results).
 
-  python tools/sweep_stencil.py --ops gauss5,box3 --env IDN_STENCIL_MAP=0,1,2 --env IDN_BAND_ROWS=0,16,36
+  python tools/sweep_stencil.py --ops gauss5,box3 --env IDN_STRIPE_MAP=0,1,2 --env IDN_BAND_ROWS=0,16,36
+
+The stencil's knobs (tuning build): IDN_STENCIL_{FORM,NTP,NTS,IDENT,GLDS,SAUX,LAUX}, IDN_STRIPE_MAP,
+IDN_BAND_ROWS, IDN_FORCE_GENERIC.
 """
 import argparse
 import itertools
