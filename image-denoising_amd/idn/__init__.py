@@ -12,7 +12,7 @@ from .ops import (  # noqa: F401
     periodic_pattern,
     add_pattern, periodic_noise, blob, mse, psnr, ssim, nl_means,
     nl_means_colored, denoise_tv_chambolle, estimate_sigma, denoise_wavelet,
-    equalize_hist, clahe, cvt_color_yuv, correct_exposure, wiener,
+    equalize_hist, clahe, cvt_color_yuv, correct_exposure, wiener, denoise_dct,
 )
 from . import automold  # noqa: F401
 

@@ -108,6 +108,9 @@ SIGNATURES = {
     "idn_wiener_u8": (_c_int, [_c_u8p, _c_u8p, _c_f64p, _c_int, _c_int, _c_int, _c_int, _c_i64,
                                _c_int, _c_int, _c_int, _c_f64p, _c_i64, _c_f64p, _c_vp, _c_size,
                                _c_vp]),
+    "idn_dct_denoise_workspace_size": (_c_size, [_c_int, _c_int, _c_int, _c_int]),
+    "idn_dct_denoise_u8": (_c_int, [_c_u8p, _c_u8p, _c_vp, _c_int, _c_int, _c_int, _c_int, _c_i64,
+                                    _c_int, _c_int, _c_f64p, _c_i64, _c_dbl, _c_vp, _c_size, _c_vp]),
     "idn_metrics_workspace_size": (_c_size, [_c_int, _c_int, _c_int, _c_int, _c_int]),
     "idn_mse_u8": (_c_int, [_c_u8p, _c_u8p, _c_f64p, _c_int, _c_int, _c_int, _c_int, _c_i64, _c_i64,
                             _c_vp, _c_size, _c_vp]),

@@ -19,6 +19,7 @@ the OpenCV / scikit-image calls the reference makes on its preprocessing path:
   denoise_tv_chambolle(x, weight, eps, n) skimage.restoration.denoise_tv_chambolle (0.14.2)
   estimate_sigma(x, average_sigmas)       skimage.restoration.estimate_sigma (multichannel=True)
   wiener(x, ksize, noise, border=...)     scipy.signal.wiener per channel plane (1.15.3)
+  denoise_dct(x, sigma, color=...)        sliding 8x8 DCT hard threshold (Yu & Sapiro, IPOL 2011)
   equalize_hist(x)                        cv2.equalizeHist(x)
   clahe(x, clip_limit, tile_grid)         cv2.createCLAHE(clip_limit, tile_grid).apply(x)
   cvt_color_yuv(x, to_yuv)                cv2.cvtColor(x, COLOR_BGR2YUV / COLOR_YUV2BGR)
@@ -61,8 +62,9 @@ from .exposure import (  # noqa: F401
     correct_exposure, cvt_color_yuv, equalize_hist,
 )
 from .restoration import (  # noqa: F401
-    TV_MAX_ITER, WIENER_BORDERS, WIENER_MAX_KSIZE, WIENER_TILE, _sigma_check, _tv_check,
-    _wiener_check, denoise_tv_chambolle, estimate_sigma, wiener,
+    DCT_PATCH, DCT_TILE, TV_MAX_ITER, WIENER_BORDERS, WIENER_MAX_KSIZE, WIENER_TILE, _dct_check,
+    _sigma_check, _tv_check, _wiener_check, denoise_dct, denoise_tv_chambolle, estimate_sigma,
+    wiener,
 )
 from .metrics import _check_pair, mse, psnr, ssim  # noqa: F401
 from .jpeg import (  # noqa: F401

@@ -131,7 +131,9 @@ typedef enum idn_wavelet_mode {
  *      added, idn_gaussian_blur_u8 and idn_box_blur_u8 accept every odd ksize 3..31 (no
  *      signature changed); later,
  *      under the same number, the adaptive median filter: idn_adaptive_median_u8 added (no
- *      signature changed) */
+ *      signature changed); later, under the
+ *      same number, the sliding DCT denoiser: idn_dct_denoise_workspace_size and
+ *      idn_dct_denoise_u8 added (no signature changed) */
 #define IDN_ABI_VERSION 11
 int idn_abi_version(void);
 const char* idn_version(void);
@@ -619,6 +621,47 @@ int idn_wiener_u8(const uint8_t* src, uint8_t* dst_u8, double* dst_f64, int n, i
                   int64_t row_stride, int kh, int kw, int border, const double* noise,
                   int64_t noise_image_stride, double* noise_out, void* workspace, size_t ws_bytes,
                   void* stream);
+
+/* ---- sliding DCT denoiser (Yu & Sapiro, IPOL 2011: 8x8 DCT, hard threshold, aggregation) ---- */
+
+/* Not a reference interface: the transform-domain denoiser of the bank, the self-contained form
+ * of "keep the strong coefficients of a redundant transform and invert".  For every plane k of
+ * every image and every patch P with the top-left corner (i, j), 0 <= i <= h-8, 0 <= j <= w-8:
+ *   D = Cm P Cm^T            (Cm: the orthonormal 8-point DCT-II matrix)
+ *   D'[u][v] = D[u][v] if (u, v) == (0, 0) or |D[u][v]| >= T_k, else 0
+ *   R = Cm^T D' Cm
+ * and r_k[y][x] is the sum of R at (y, x) over the patches that contain it, divided by their
+ * number, (min(y,h-8) - max(y-7,0) + 1) * (min(x,w-8) - max(x-7,0) + 1).  Nothing is decimated.
+ * color = 0: the planes are the channels, T_k = factor * sigma_k.  color = 1 (c = 3 only): the
+ * planes are g_k = sum_j M[k][j] x_j with M the orthonormal 3-point DCT on the channels as stored
+ * (rows [1,1,1]/sqrt3, [1,0,-1]/sqrt2, [1,-2,1]/sqrt6), T_k = factor * sqrt(sum_j M[k][j]^2
+ * sigma_j^2), the exact propagation of the noise, and the result is r_j = sum_k M[k][j] r_k.
+ * sigma: device array of doubles on the 0..255 scale (what idn_estimate_sigma writes), read at
+ * sigma[i*sigma_image_stride + ch] (sigma_image_stride c, or 0 when one row of c values serves
+ * every image), not validated: a NaN keeps the DC terms only.  sigma 0 returns the input.
+ * dst_f32 (n*h*w*c floats, compact) receives r, dst_u8 (src's layout) clip(rint(r), 0, 255),
+ * round half to even; either may be NULL, not both.
+ * fp32 arithmetic.  tests/dct_model.py (numpy float64) is the definition; the device result lies
+ * within a few 1e-4 of it wherever no coefficient is within rounding of its threshold (a flipped
+ * coefficient moves a sample by up to about 0.6), and has the same bits on every call and in
+ * every batch: every sum has a fixed order, nothing is an atomic.  Parity with
+ * cv2.xphoto.dctDenoising and the IPOL code is unpinned: here the DC term always stays, the patch
+ * is 8, the colour transform is fixed and there is no PCA.
+ * One launch; each lane walks a patch column down the image with the row transforms in a
+ * register ring, 18 one-dimensional transforms per patch (csrc/dct_denoise.hip).
+ * Stream-ordered and capture-safe: no allocation, host copy or synchronisation.
+ * workspace: idn_dct_denoise_workspace_size(n, h, w, c) bytes, which is 0 (the thresholds are
+ *   formed in the kernel's prologue): workspace may be NULL, and IDN_EWORKSPACE cannot occur.
+ * IDN_EINVAL: null src or sigma, both destinations null, dst_u8 == src, n < 0, h or w < 1, c not
+ *   1 or 3, row_stride < w*c, color not 0 or 1, color 1 with c 1, dst_f32 not 4-byte or sigma
+ *   not 8-byte aligned, sigma_image_stride neither 0 nor c, factor negative, NaN or infinite.
+ *   IDN_EUNSUPPORTED: patch other than 8 (16 is not built), h or w below 8.  n == 0 returns
+ *   IDN_OK without a launch.  Every argument check runs before any HIP call. */
+size_t idn_dct_denoise_workspace_size(int n, int h, int w, int c);
+int idn_dct_denoise_u8(const uint8_t* src, uint8_t* dst_u8, float* dst_f32, int n, int h, int w,
+                       int c, int64_t row_stride, int patch, int color, const double* sigma,
+                       int64_t sigma_image_stride, double factor, void* workspace,
+                       size_t ws_bytes, void* stream);
 
 /* ---- quality metrics (skimage 0.14.2 measure.compare_mse / compare_psnr / compare_ssim) ---- */
 
