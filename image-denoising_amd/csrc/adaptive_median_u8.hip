@@ -27,6 +27,7 @@
 // to k + 2 through the 4 (k + 1) samples of the new ring in the staged tile, O(k) per level, and
 // the bisection counts over the tile.
 #include "idn_common.hpp"
+#include "abi_args.hpp"
 
 namespace idn {
 

@@ -15,6 +15,7 @@
 // (b, g) / (r, wsum) accumulate as packed fp32 pairs.  The weights are then exactly OpenCV's;
 // only the fp32 summation order differs (<= 1 LSB after cvRound).
 #include "idn_common.hpp"
+#include "abi_args.hpp"
 
 #include <math.h>
 #include <string.h>
@@ -533,7 +534,7 @@ extern "C" int idn_bilateral_u8(const uint8_t* src, uint8_t* dst, int n, int h, 
                                 void* stream) {
   using namespace idn;
   if (int e = check_filter_args(src, dst, n, h, w, c, row_stride, "idn_bilateral_u8")) return e;
-  IDN_CHECK_ARG(c == 1 || c == 3, "idn_bilateral_u8: channels must be 1 or 3 (got %d)", c);
+  if (int e = check_channels_1_or_3("idn_bilateral_u8", c)) return e;
   if (n == 0) return IDN_OK;
   if (sigma_color <= 0) sigma_color = 1;
   if (sigma_space <= 0) sigma_space = 1;

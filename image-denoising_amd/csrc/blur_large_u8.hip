@@ -29,7 +29,8 @@
 // reach the multiply-adds through v_readlane (the loop counter is uniform): no tap is read from
 // memory inside the loops.  Every tap is a byte: a centre tap of 256 is the identity and runs
 // bl_copy_kernel.
-#include "idn_common.hpp"
+#include "blur_large.hpp"
+#include "abi_args.hpp"
 
 #include <limits.h>
 #include <math.h>
@@ -361,7 +362,7 @@ static int bl_grid(int n, int h, int64_t wb, int tw, int sr, int* tiles, int* st
                    unsigned* grid, const char* name) {
   const int64_t nt = (wb + tw - 1) / tw, nst = ((int64_t)h + sr - 1) / sr;
   if (wb > INT_MAX - BL_KMAX * 4 - BL_TW || (int64_t)n * nt * nst > INT_MAX)
-    return set_error(IDN_EUNSUPPORTED, "%s: batch too large for one launch", name);
+    return batch_too_large(name);
   *tiles = (int)nt;
   *strips = (int)nst;
   *grid = (unsigned)((int64_t)n * nt * nst);

@@ -25,6 +25,7 @@
 // one row ahead.  A patch column or row outside the image is computed on clamped addresses and
 // contributes zeros.
 #include "idn_common.hpp"
+#include "abi_args.hpp"
 #include "dct8.hpp"
 
 #include <limits.h>
@@ -215,11 +216,8 @@ extern "C" int idn_dct_denoise_u8(const uint8_t* src, uint8_t* dst_u8, float* ds
   const char* name = "idn_dct_denoise_u8";
   IDN_CHECK_ARG(src && sigma, "%s: null pointer (src or sigma)", name);
   IDN_CHECK_ARG(dst_u8 || dst_f32, "%s: both destinations are null", name);
-  IDN_CHECK_ARG(dst_u8 != src, "%s: in-place filtering is not supported (dst_u8 == src)", name);
-  IDN_CHECK_ARG(n >= 0 && h >= 1 && w >= 1, "%s: bad shape n=%d h=%d w=%d", name, n, h, w);
-  IDN_CHECK_ARG(c == 1 || c == 3, "%s: channels must be 1 or 3 (got %d)", name, c);
-  IDN_CHECK_ARG(row_stride >= (int64_t)w * c, "%s: row_stride %lld < w*c", name,
-                (long long)row_stride);
+  if (int e = check_not_in_place(name, src, dst_u8, "dst_u8 == src")) return e;
+  if (int e = check_image_1_or_3(name, n, h, w, c, row_stride)) return e;
   IDN_CHECK_ARG(color == 0 || (color == 1 && c == 3),
                 "%s: color must be 0, or 1 with 3 channels (got %d with %d)", name, color, c);
   IDN_CHECK_ARG(((uintptr_t)dst_f32 & 3) == 0, "%s: dst_f32 must be 4-byte aligned", name);
@@ -240,7 +238,7 @@ extern "C" int idn_dct_denoise_u8(const uint8_t* src, uint8_t* dst_u8, float* ds
   const int sr = DD_SR;
   const int64_t tiles = ((int64_t)w + DD_TW - 1) / DD_TW, strips = ((int64_t)h + sr - 1) / sr;
   if ((int64_t)w * c > INT_MAX - 256 || (int64_t)n * tiles * strips > INT_MAX)
-    return set_error(IDN_EUNSUPPORTED, "%s: batch too large for one launch", name);
+    return batch_too_large(name);
 
   const hipStream_t s = as_stream(stream);
   const unsigned grid = (unsigned)((int64_t)n * tiles * strips);

@@ -23,6 +23,7 @@
 // the later passes at once.  Counts are integers and the list is ranked by value, so no result
 // depends on the order of execution; one workgroup never straddles two planes.
 #include "idn_common.hpp"
+#include "abi_args.hpp"
 
 #include <limits.h>
 
@@ -60,11 +61,12 @@ struct SigLayout {
 
 static SigLayout sig_layout(int64_t planes) {
   SigLayout L;
-  L.state = 0;
-  L.lcnt = L.state + (size_t)planes * sizeof(SigState);
-  L.hist = L.lcnt + (size_t)planes * 2 * sizeof(uint32_t);
-  L.list = L.hist + (size_t)planes * 2 * SIG_BINS * sizeof(uint32_t);
-  L.total = L.list + (size_t)planes * 2 * SIG_CAP * sizeof(uint64_t);
+  Bump ws;
+  L.state = ws.take((size_t)planes * sizeof(SigState));
+  L.lcnt = ws.take((size_t)planes * 2 * sizeof(uint32_t));
+  L.hist = ws.take((size_t)planes * 2 * SIG_BINS * sizeof(uint32_t));
+  L.list = ws.take((size_t)planes * 2 * SIG_CAP * sizeof(uint64_t));
+  L.total = ws.total;
   return L;
 }
 
@@ -388,10 +390,7 @@ extern "C" int idn_estimate_sigma(const uint8_t* src_u8, const double* src_f64, 
   IDN_CHECK_ARG((src_u8 != nullptr) != (src_f64 != nullptr),
                 "%s: exactly one of src_u8 and src_f64 must be given (null pointer otherwise)", name);
   IDN_CHECK_ARG(dst, "%s: null pointer (dst)", name);
-  IDN_CHECK_ARG(n >= 0 && h >= 1 && w >= 1, "%s: bad shape n=%d h=%d w=%d", name, n, h, w);
-  IDN_CHECK_ARG(c == 1 || c == 3, "%s: channels must be 1 or 3 (got %d)", name, c);
-  IDN_CHECK_ARG(row_stride >= (int64_t)w * c, "%s: row_stride %lld < w*c", name,
-                (long long)row_stride);
+  if (int e = check_image_1_or_3(name, n, h, w, c, row_stride)) return e;
   IDN_CHECK_ARG(!src_f64 || ((uintptr_t)src_f64 & 7) == 0, "%s: src_f64 must be 8-byte aligned",
                 name);
   IDN_CHECK_ARG(((uintptr_t)dst & 7) == 0, "%s: dst must be 8-byte aligned", name);
@@ -406,12 +405,9 @@ extern "C" int idn_estimate_sigma(const uint8_t* src_u8, const double* src_f64, 
   const int tiles_x = (ow + SIG_TW - 1) / SIG_TW, tiles_y = (oh + th - 1) / th;
   if ((int64_t)w * c > INT_MAX || planes * tiles_x * tiles_y > INT_MAX ||
       (int64_t)oh * ow > (int64_t)UINT_MAX)
-    return set_error(IDN_EUNSUPPORTED, "%s: batch too large for one launch", name);
+    return batch_too_large(name);
   const SigLayout L = sig_layout(planes);
-  if (!workspace || ws_bytes < L.total)
-    return set_error(IDN_EWORKSPACE, "%s: workspace of %zu bytes needed, %zu given", name, L.total,
-                     workspace ? ws_bytes : (size_t)0);
-  IDN_CHECK_ARG(((uintptr_t)workspace & 7) == 0, "%s: workspace must be 8-byte aligned", name);
+  if (int e = check_workspace(name, workspace, ws_bytes, L.total)) return e;
 
   char* base = static_cast<char*>(workspace);
   SigState* st = reinterpret_cast<SigState*>(base + L.state);

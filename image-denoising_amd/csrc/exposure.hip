@@ -35,6 +35,7 @@
 // 15 bytes, where the seven separate steps (two conversions, the tone step, two CLAHE, equalizeHist)
 // would move 23.
 #include "idn_common.hpp"
+#include "abi_args.hpp"
 
 #include <limits.h>
 #include <math.h>
@@ -431,38 +432,16 @@ struct ExpLayout {
   size_t hist, ihist, luts, eq, plane, total;
 };
 
-static size_t exp_up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 static ExpLayout exp_layout(int n, int h, int w, int tiles) {
   ExpLayout l;
-  l.hist = 0;
-  l.ihist = l.hist + (size_t)n * tiles * 256 * sizeof(uint32_t);
-  l.luts = l.ihist + (size_t)n * 256 * sizeof(uint32_t);
-  l.eq = l.luts + (size_t)n * tiles * 256;
-  l.plane = l.eq + (size_t)n * 256;
-  l.total = exp_up256(l.plane + (size_t)n * h * w);
+  Bump ws;
+  l.hist = ws.take((size_t)n * tiles * 256 * sizeof(uint32_t));
+  l.ihist = ws.take((size_t)n * 256 * sizeof(uint32_t));
+  l.luts = ws.take((size_t)n * tiles * 256);
+  l.eq = ws.take((size_t)n * 256);
+  l.plane = ws.take((size_t)n * h * w);
+  l.total = align_up(ws.total, 256);
   return l;
-}
-
-static int exp_check_image(const uint8_t* src, uint8_t* dst, int n, int h, int w, int c,
-                           int64_t row_stride, const char* name) {
-  IDN_CHECK_ARG(src && dst, "%s: null pointer", name);
-  IDN_CHECK_ARG(src != dst, "%s: in-place operation is not supported (src == dst)", name);
-  IDN_CHECK_ARG(n >= 0 && h > 0 && w > 0, "%s: bad shape n=%d h=%d w=%d", name, n, h, w);
-  IDN_CHECK_ARG(row_stride >= (int64_t)w * c, "%s: row_stride %lld < w*%d", name,
-                (long long)row_stride, c);
-  return IDN_OK;
-}
-
-static int exp_check_workspace(int n, int h, int w, int tiles, void* workspace,
-                               size_t workspace_bytes, const char* name) {
-  if (n == 0) return IDN_OK;
-  const size_t need = exp_layout(n, h, w, tiles).total;
-  if (!workspace || workspace_bytes < need)
-    return set_error(IDN_EWORKSPACE, "%s: workspace of %zu bytes needed, %zu given", name, need,
-                     workspace ? workspace_bytes : (size_t)0);
-  IDN_CHECK_ARG(((uintptr_t)workspace & 7) == 0, "%s: workspace must be 8-byte aligned", name);
-  return IDN_OK;
 }
 
 // what one launch can index: a histogram workgroup per EXP_HR tile rows, pixels of a tile in int
@@ -504,36 +483,30 @@ static void exp_launch_apply(hipStream_t st, ExpApply a, int n, const ExpGeom& g
                      dim3(256), lds, st, a, g);
 }
 
-}  // namespace idn
-
-extern "C" int idn_bgr2yuv_u8(const uint8_t* src, uint8_t* dst, int n, int h, int w,
-                              int64_t row_stride, void* stream) {
-  using namespace idn;
-  const char* const name = "idn_bgr2yuv_u8";
-  if (int e = exp_check_image(src, dst, n, h, w, 3, row_stride, name)) return e;
+template <bool TO_YUV>
+static int exp_cvt(const uint8_t* src, uint8_t* dst, int n, int h, int w, int64_t row_stride,
+                   void* stream, const char* name) {
+  if (int e = check_src_dst(name, src, dst, n, h, w, "operation")) return e;
+  if (int e = check_row_stride(name, row_stride, w, 3, "3")) return e;
   if (n == 0) return IDN_OK;
   const int xblocks = (w + 255) / 256;
-  if ((int64_t)n * h * xblocks > (int64_t)INT_MAX)
-    return set_error(IDN_EUNSUPPORTED, "%s: batch too large for one launch", name);
-  hipLaunchKernelGGL((exp_cvt_kernel<true>), dim3((unsigned)(n * h * xblocks)), dim3(256), 0,
+  if ((int64_t)n * h * xblocks > (int64_t)INT_MAX) return batch_too_large(name);
+  hipLaunchKernelGGL((exp_cvt_kernel<TO_YUV>), dim3((unsigned)(n * h * xblocks)), dim3(256), 0,
                      as_stream(stream), src, dst, w, row_stride, xblocks);
   IDN_CHECK_LAUNCH(name);
   return IDN_OK;
 }
 
+}  // namespace idn
+
+extern "C" int idn_bgr2yuv_u8(const uint8_t* src, uint8_t* dst, int n, int h, int w,
+                              int64_t row_stride, void* stream) {
+  return idn::exp_cvt<true>(src, dst, n, h, w, row_stride, stream, "idn_bgr2yuv_u8");
+}
+
 extern "C" int idn_yuv2bgr_u8(const uint8_t* src, uint8_t* dst, int n, int h, int w,
                               int64_t row_stride, void* stream) {
-  using namespace idn;
-  const char* const name = "idn_yuv2bgr_u8";
-  if (int e = exp_check_image(src, dst, n, h, w, 3, row_stride, name)) return e;
-  if (n == 0) return IDN_OK;
-  const int xblocks = (w + 255) / 256;
-  if ((int64_t)n * h * xblocks > (int64_t)INT_MAX)
-    return set_error(IDN_EUNSUPPORTED, "%s: batch too large for one launch", name);
-  hipLaunchKernelGGL((exp_cvt_kernel<false>), dim3((unsigned)(n * h * xblocks)), dim3(256), 0,
-                     as_stream(stream), src, dst, w, row_stride, xblocks);
-  IDN_CHECK_LAUNCH(name);
-  return IDN_OK;
+  return idn::exp_cvt<false>(src, dst, n, h, w, row_stride, stream, "idn_yuv2bgr_u8");
 }
 
 extern "C" size_t idn_exposure_workspace_size(int n, int h, int w, int tiles_x, int tiles_y) {
@@ -547,12 +520,13 @@ extern "C" int idn_equalize_hist_u8(const uint8_t* src, uint8_t* dst, int n, int
                                     void* stream) {
   using namespace idn;
   const char* const name = "idn_equalize_hist_u8";
-  if (int e = exp_check_image(src, dst, n, h, w, 1, row_stride, name)) return e;
-  if (int e = exp_check_workspace(n, h, w, 1, workspace, workspace_bytes, name)) return e;
+  if (int e = check_src_dst(name, src, dst, n, h, w, "operation")) return e;
+  if (int e = check_row_stride(name, row_stride, w, 1, "1")) return e;
   if (n == 0) return IDN_OK;
+  const ExpLayout l = exp_layout(n, h, w, 1);
+  if (int e = check_workspace(name, workspace, workspace_bytes, l.total)) return e;
   const ExpGeom g = exp_geom(h, w, 1, 1);
   if (int e = exp_check_size(n, g, name)) return e;
-  const ExpLayout l = exp_layout(n, h, w, 1);
   uint8_t* ws = static_cast<uint8_t*>(workspace);
   uint32_t* ihist = reinterpret_cast<uint32_t*>(ws + l.ihist);
   const hipStream_t st = as_stream(stream);
@@ -576,7 +550,8 @@ extern "C" int idn_clahe_u8(const uint8_t* src, uint8_t* dst, int n, int h, int 
                             void* workspace, size_t workspace_bytes, void* stream) {
   using namespace idn;
   const char* const name = "idn_clahe_u8";
-  if (int e = exp_check_image(src, dst, n, h, w, 1, row_stride, name)) return e;
+  if (int e = check_src_dst(name, src, dst, n, h, w, "operation")) return e;
+  if (int e = check_row_stride(name, row_stride, w, 1, "1")) return e;
   IDN_CHECK_ARG(exp_grid_ok(tiles_x, tiles_y), "%s: tiles_x and tiles_y must be in 1..%d (got %d, "
                 "%d)", name, EXP_MAX_TILES, tiles_x, tiles_y);
   IDN_CHECK_ARG(h > tiles_y && w > tiles_x, "%s: image %d x %d needs more rows and columns than "
@@ -584,11 +559,11 @@ extern "C" int idn_clahe_u8(const uint8_t* src, uint8_t* dst, int n, int h, int 
   IDN_CHECK_ARG(clip_limit >= 0.0 && clip_limit < INFINITY, "%s: clip_limit must be finite and "
                 "not negative (got %g)", name, clip_limit);
   const int tiles = tiles_x * tiles_y;
-  if (int e = exp_check_workspace(n, h, w, tiles, workspace, workspace_bytes, name)) return e;
   if (n == 0) return IDN_OK;
+  const ExpLayout l = exp_layout(n, h, w, tiles);
+  if (int e = check_workspace(name, workspace, workspace_bytes, l.total)) return e;
   const ExpGeom g = exp_geom(h, w, tiles_x, tiles_y);
   if (int e = exp_check_size(n, g, name)) return e;
-  const ExpLayout l = exp_layout(n, h, w, tiles);
   uint8_t* ws = static_cast<uint8_t*>(workspace);
   uint32_t* hist = reinterpret_cast<uint32_t*>(ws + l.hist);
   const hipStream_t st = as_stream(stream);
@@ -621,14 +596,15 @@ extern "C" int idn_correct_exposure_u8(const uint8_t* src, uint8_t* dst, int n, 
   const char* const name = "idn_correct_exposure_u8";
   constexpr int TX = 4, TY = 4, TILES = TX * TY;  // createCLAHE(clipLimit=2.0, tileGridSize=(4,4))
   constexpr double CLIP_LIMIT = 2.0;
-  if (int e = exp_check_image(src, dst, n, h, w, 3, row_stride, name)) return e;
+  if (int e = check_src_dst(name, src, dst, n, h, w, "operation")) return e;
+  if (int e = check_row_stride(name, row_stride, w, 3, "3")) return e;
   IDN_CHECK_ARG(h > TY && w > TX, "%s: image %d x %d needs more rows and columns than the %d x %d "
                 "tile grid", name, h, w, TY, TX);
-  if (int e = exp_check_workspace(n, h, w, TILES, workspace, workspace_bytes, name)) return e;
   if (n == 0) return IDN_OK;
+  const ExpLayout l = exp_layout(n, h, w, TILES);
+  if (int e = check_workspace(name, workspace, workspace_bytes, l.total)) return e;
   const ExpGeom g = exp_geom(h, w, TX, TY);
   if (int e = exp_check_size(n, g, name)) return e;
-  const ExpLayout l = exp_layout(n, h, w, TILES);
   uint8_t* ws = static_cast<uint8_t*>(workspace);
   uint32_t* hist = reinterpret_cast<uint32_t*>(ws + l.hist);
   uint32_t* ihist = reinterpret_cast<uint32_t*>(ws + l.ihist);

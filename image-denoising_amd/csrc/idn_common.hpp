@@ -13,16 +13,6 @@ namespace idn {
 
 // ---- error plumbing (thread-local message, negative status) --------------------------------
 int set_error(int status, const char* fmt, ...);
-// shared argument validation of the u8 -> u8 filters (defined in stencil_u8.hip)
-int check_filter_args(const uint8_t* src, uint8_t* dst, int n, int h, int w, int c,
-                      int64_t row_stride, const char* name);
-// the wide smoothers and the host's Q8 Gaussian taps (defined in blur_large_u8.hip)
-int gaussian_taps(int ksize, double sigma, uint16_t* taps, const char* name);
-int launch_box_large(const uint8_t* src, uint8_t* dst, int n, int h, int w, int c,
-                     int64_t row_stride, int k, hipStream_t s, const char* name);
-int launch_gauss_large(const uint8_t* src, uint8_t* dst, int n, int h, int w, int c,
-                       int64_t row_stride, int ksize, const uint16_t* taps, hipStream_t s,
-                       const char* name);
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
 #define IDN_CHECK_ARG(cond, ...)                                         \

@@ -99,9 +99,9 @@ extern "C" int idn_jpeg_decode_u8(const uint8_t* const* files, const size_t* len
   std::string err;
   const int rc = jpeg_plan(files, lens, n, h, w, flags, P, &err);
   if (rc != IDN_OK) return set_error(rc, "idn_jpeg_decode_u8: %s", err.c_str());
-  if (!workspace || ws_bytes < P.total)
-    return set_error(IDN_EWORKSPACE, "idn_jpeg_decode_u8: needs %zu workspace bytes (got %zu)",
-                     P.total, ws_bytes);
+  if (int e = check_workspace_got("idn_jpeg_decode_u8", workspace, ws_bytes, P.total,
+                                  IDN_EWORKSPACE))
+    return e;
   hipStream_t st = as_stream(stream);
   uint8_t* ws = static_cast<uint8_t*>(workspace);
   // one pinned host staging buffer (kept per thread, grown as needed; the call is synchronous, so

@@ -12,6 +12,7 @@
 #include <string>
 #include <vector>
 
+#include "abi_args.hpp"
 #include "jpeg_desc.hpp"
 
 namespace idn {
@@ -490,9 +491,9 @@ inline int jpg_color_space(const JpegHost& J, bool turbo) {
 }
 
 // ---- host: batch plan ---------------------------------------------------------------------------
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-struct JpegPlan {
+// the workspace regions are carved by Bump::take, each on a 256-byte boundary
+struct JpegPlan : Bump {
+  JpegPlan() { align = 256; }
   std::vector<JpegDev> dev;
   std::vector<uint64_t> blk_end;
   std::vector<size_t> scan_begin;
@@ -505,18 +506,12 @@ struct JpegPlan {
   bool any_chunked = false, any_restart = false;
   bool any_huff_scan = false, any_arith = false;  // scan-path images of each coding
   bool scales[2][2] = {};  // IDCT output scales present: [sv - 1][sh - 1]
-  // workspace regions, in this order, each 256-byte aligned (take); the entry point stages
+  // workspace regions, in this order, each 256-byte aligned; the entry point stages
   // [off_imgs, off_coef) through pinned memory in one piece
   size_t off_imgs = 0, off_blkend = 0, off_scans = 0, off_scan = 0, off_coef = 0, off_planes = 0;
   size_t off_ub = 0, off_iv = 0, off_ivend = 0, off_mk = 0, off_ublen = 0, off_ublen_s = 0, off_s0 = 0, off_s1 = 0,
          off_cnt = 0, off_start = 0, off_flag = 0, off_chg0 = 0, off_chg1 = 0, off_ck_st = 0,
-         off_ck_co = 0, off_tcnt = 0, off_ck_iv = 0, off_iv_ck = 0, total = 0;
-  // the next region: its offset; total moves past its bytes to the next 256-byte boundary
-  size_t take(size_t bytes) {
-    const size_t off = total;
-    total = align256(total + bytes);
-    return off;
-  }
+         off_ck_co = 0, off_tcnt = 0, off_ck_iv = 0, off_iv_ck = 0;
 };
 
 // flags: IDN_JPEG_TURBO selects libjpeg-turbo's decode (else libjpeg 9d's); bits 8..23 = entropy

@@ -16,6 +16,7 @@
 //        generated and proven by tools/gen_median_cols.py with the 0-1 principle).  ~55 min/max
 //        per output byte pair instead of 202 for the unsorted 25-input network.
 #include "stripe.hpp"
+#include "abi_args.hpp"
 #include "median_cols.hpp"
 
 namespace idn {

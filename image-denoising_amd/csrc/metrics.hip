@@ -29,6 +29,7 @@
 // mse_final_kernel and divided once in float64: bit-equal to numpy's mean of the squared
 // float64 differences, whose partial sums all stay below 2^53.
 #include "idn_common.hpp"
+#include "abi_args.hpp"
 
 #include <limits.h>
 
@@ -289,12 +290,12 @@ static int64_t mse_wgs(int h, int w, int c, bool compact) {
 }
 
 static bool win_ok(int win) { return win >= 3 && win <= 11 && (win & 1); }
-
-static int check_pair_args(const uint8_t* a, const uint8_t* b, int n, int h, int w, int c,
-                           int64_t row_stride_a, int64_t row_stride_b, const char* name) {
+// the two images of a metric; their pointers and strides are worded together
+static int check_pair(const char* name, const uint8_t* a, const uint8_t* b, int n, int h, int w,
+                      int c, int64_t row_stride_a, int64_t row_stride_b) {
   IDN_CHECK_ARG(a && b, "%s: null pointer", name);
-  IDN_CHECK_ARG(n >= 0 && h > 0 && w > 0, "%s: bad shape n=%d h=%d w=%d", name, n, h, w);
-  IDN_CHECK_ARG(c == 1 || c == 3, "%s: channels must be 1 or 3 (got %d)", name, c);
+  if (int e = check_shape(name, n, h, w)) return e;
+  if (int e = check_channels_1_or_3(name, c)) return e;
   IDN_CHECK_ARG(row_stride_a >= (int64_t)w * c && row_stride_b >= (int64_t)w * c,
                 "%s: row_stride %lld / %lld < w*c", name, (long long)row_stride_a,
                 (long long)row_stride_b);
@@ -331,7 +332,7 @@ extern "C" int idn_mse_u8(const uint8_t* a, const uint8_t* b, double* mse_out, i
                           int c, int64_t row_stride_a, int64_t row_stride_b, void* workspace,
                           size_t workspace_bytes, void* stream) {
   using namespace idn;
-  if (int e = check_pair_args(a, b, n, h, w, c, row_stride_a, row_stride_b, "idn_mse_u8")) return e;
+  if (int e = check_pair("idn_mse_u8", a, b, n, h, w, c, row_stride_a, row_stride_b)) return e;
   IDN_CHECK_ARG(mse_out, "idn_mse_u8: null pointer (mse_out)");
   if (n == 0) return IDN_OK;
   const int64_t wc = (int64_t)w * c;
@@ -340,12 +341,8 @@ extern "C" int idn_mse_u8(const uint8_t* a, const uint8_t* b, double* mse_out, i
   const bool compact = row_stride_a == wc && row_stride_b == wc;
   const int64_t wgs = mse_wgs(h, w, c, compact);
   const size_t need = (size_t)n * (size_t)wgs * sizeof(uint64_t);
-  if (!workspace || workspace_bytes < need)
-    return set_error(IDN_EWORKSPACE, "idn_mse_u8: workspace of %zu bytes needed, %zu given", need,
-                     workspace ? workspace_bytes : (size_t)0);
-  IDN_CHECK_ARG(((uintptr_t)workspace & 7) == 0, "idn_mse_u8: workspace must be 8-byte aligned");
-  if ((int64_t)n * wgs > (int64_t)INT_MAX)
-    return set_error(IDN_EUNSUPPORTED, "idn_mse_u8: batch too large for one launch");
+  if (int e = check_workspace("idn_mse_u8", workspace, workspace_bytes, need)) return e;
+  if ((int64_t)n * wgs > (int64_t)INT_MAX) return batch_too_large("idn_mse_u8");
   const uint32_t rows = compact ? 1u : (uint32_t)h;
   const uint32_t rowlen = compact ? (uint32_t)(h * wc) : (uint32_t)wc;
   const uint32_t upr = (rowlen + 15u) / 16u;
@@ -366,7 +363,7 @@ extern "C" int idn_ssim_u8(const uint8_t* a, const uint8_t* b, double* ssim_out,
                            int64_t row_stride_a, int64_t row_stride_b, int win_size,
                            void* workspace, size_t workspace_bytes, void* stream) {
   using namespace idn;
-  if (int e = check_pair_args(a, b, n, h, w, c, row_stride_a, row_stride_b, "idn_ssim_u8")) return e;
+  if (int e = check_pair("idn_ssim_u8", a, b, n, h, w, c, row_stride_a, row_stride_b)) return e;
   IDN_CHECK_ARG(ssim_out, "idn_ssim_u8: null pointer (ssim_out)");
   IDN_CHECK_ARG(win_ok(win_size), "idn_ssim_u8: win_size must be odd and in 3..11 (got %d)",
                 win_size);
@@ -376,12 +373,8 @@ extern "C" int idn_ssim_u8(const uint8_t* a, const uint8_t* b, double* ssim_out,
   const SsimGeom g = ssim_geom(h, w, c, win_size);
   const int64_t wgs = (int64_t)g.tiles * g.strips;
   const size_t need = (size_t)n * (size_t)wgs * 4 * sizeof(double);
-  if (!workspace || workspace_bytes < need)
-    return set_error(IDN_EWORKSPACE, "idn_ssim_u8: workspace of %zu bytes needed, %zu given", need,
-                     workspace ? workspace_bytes : (size_t)0);
-  IDN_CHECK_ARG(((uintptr_t)workspace & 7) == 0, "idn_ssim_u8: workspace must be 8-byte aligned");
-  if ((int64_t)n * wgs > (int64_t)INT_MAX)
-    return set_error(IDN_EUNSUPPORTED, "idn_ssim_u8: batch too large for one launch");
+  if (int e = check_workspace("idn_ssim_u8", workspace, workspace_bytes, need)) return e;
+  if ((int64_t)n * wgs > (int64_t)INT_MAX) return batch_too_large("idn_ssim_u8");
   const double np = (double)(win_size * win_size);
   const double c1 = (0.01 * 255.0) * (0.01 * 255.0), c2 = (0.03 * 255.0) * (0.03 * 255.0);
   const double c1s = c1 * (np * np), c2s = c2 * (np * (np - 1.0));

@@ -45,6 +45,7 @@
 // The cbrt table (and LabToYF_b for the way back) is staged in LDS behind the weights, before the
 // tile: these two modes have one barrier more.  NLM_PLAIN is the kernel described above.
 #include "idn_common.hpp"
+#include "abi_args.hpp"
 #include "lab_cvt.hpp"
 
 #include <limits.h>
@@ -237,8 +238,10 @@ __global__ __launch_bounds__(256) void nlmeans_kernel(const uint8_t* __restrict_
   }
 }
 
-static bool nlm_sizes_ok(int t, int s) {
-  return (t & 1) && t >= 3 && t <= 7 && (s & 1) && s >= 5 && s <= 21;
+static int nlm_check_sizes(const char* name, int t, int s) {
+  IDN_CHECK_ARG((t & 1) && t >= 3 && t <= 7 && (s & 1) && s >= 5 && s <= 21, "%s: template_size "
+                "must be odd in 3..7 and search_size odd in 5..21 (got %d, %d)", name, t, s);
+  return IDN_OK;
 }
 
 // A launch gets 64 KB of LDS without asking; a longer weight table raises the kernel's limit first
@@ -313,10 +316,8 @@ extern "C" int idn_nlmeans_weights(double h, int c, int template_size, int searc
   IDN_CHECK_ARG(cap >= 0, "idn_nlmeans_weights: negative cap %d", cap);
   IDN_CHECK_ARG(h > 0.0 && h < INFINITY, "idn_nlmeans_weights: h must be positive and finite "
                 "(got %g)", h);
-  IDN_CHECK_ARG(c == 1 || c == 3, "idn_nlmeans_weights: channels must be 1 or 3 (got %d)", c);
-  IDN_CHECK_ARG(nlm_sizes_ok(template_size, search_size),
-                "idn_nlmeans_weights: template_size must be odd in 3..7 and search_size odd in "
-                "5..21 (got %d, %d)", template_size, search_size);
+  if (int e = check_channels_1_or_3("idn_nlmeans_weights", c)) return e;
+  if (int e = nlm_check_sizes("idn_nlmeans_weights", template_size, search_size)) return e;
   *n_weights = nlm_fill_weights(h, c, template_size, search_size, wt_out, cap);
   *shift = nlm_shift(template_size);
   *fixed_point_mult = INT_MAX / (search_size * search_size * 255);
@@ -327,15 +328,11 @@ extern "C" int idn_nlmeans_u8(const uint8_t* src, uint8_t* dst, int n, int h, in
                               int64_t row_stride, int template_size, int search_size,
                               const int32_t* weights_dev, int n_weights, void* stream) {
   using namespace idn;
-  IDN_CHECK_ARG(src && dst && weights_dev, "idn_nlmeans_u8: null pointer");
-  IDN_CHECK_ARG(src != dst, "idn_nlmeans_u8: in-place filtering is not supported (src == dst)");
-  IDN_CHECK_ARG(n >= 0 && h > 0 && w > 0, "idn_nlmeans_u8: bad shape n=%d h=%d w=%d", n, h, w);
-  IDN_CHECK_ARG(c == 1 || c == 3, "idn_nlmeans_u8: channels must be 1 or 3 (got %d)", c);
-  IDN_CHECK_ARG(row_stride >= (int64_t)w * c, "idn_nlmeans_u8: row_stride %lld < w*c",
-                (long long)row_stride);
-  IDN_CHECK_ARG(nlm_sizes_ok(template_size, search_size),
-                "idn_nlmeans_u8: template_size must be odd in 3..7 and search_size odd in 5..21 "
-                "(got %d, %d)", template_size, search_size);
+  const char* const name = "idn_nlmeans_u8";
+  IDN_CHECK_ARG(src && dst && weights_dev, "%s: null pointer", name);
+  if (int e = check_not_in_place(name, src, dst)) return e;
+  if (int e = check_image_1_or_3(name, n, h, w, c, row_stride)) return e;
+  if (int e = nlm_check_sizes(name, template_size, search_size)) return e;
   const int sr = search_size / 2, b = template_size / 2 + sr;
   IDN_CHECK_ARG(h > b && w > b, "idn_nlmeans_u8: image %d x %d smaller than the %d pixels the "
                 "template and search windows need", h, w, b + 1);
@@ -347,8 +344,7 @@ extern "C" int idn_nlmeans_u8(const uint8_t* src, uint8_t* dst, int n, int h, in
   if (n == 0) return IDN_OK;
   const int tiles_x = (w + nlm_ow(template_size) - 1) / nlm_ow(template_size);
   const int tiles_y = (h + NLM_ROWS - 1) / NLM_ROWS;
-  if ((int64_t)n * tiles_x * tiles_y > (int64_t)INT_MAX)
-    return set_error(IDN_EUNSUPPORTED, "idn_nlmeans_u8: batch too large for one launch");
+  if ((int64_t)n * tiles_x * tiles_y > (int64_t)INT_MAX) return batch_too_large(name);
   const unsigned grid = (unsigned)(n * tiles_x * tiles_y);
   const size_t lds = ((size_t)NLM_PITCH * (NLM_ROWS + 2 * b) + (size_t)n_weights + 1) * 4;
   const hipStream_t st = as_stream(stream);
@@ -377,9 +373,7 @@ extern "C" int idn_nlmeans_colored_weights(double h, double h_color, int templat
                 "finite (got %g)", h);
   IDN_CHECK_ARG(h_color > 0.0 && h_color < INFINITY, "idn_nlmeans_colored_weights: h_color must "
                 "be positive and finite (got %g)", h_color);
-  IDN_CHECK_ARG(nlm_sizes_ok(template_size, search_size),
-                "idn_nlmeans_colored_weights: template_size must be odd in 3..7 and search_size "
-                "odd in 5..21 (got %d, %d)", template_size, search_size);
+  if (int e = nlm_check_sizes("idn_nlmeans_colored_weights", template_size, search_size)) return e;
   *n_l = nlm_fill_weights(h, 1, template_size, search_size, wt_l, cap_l);
   *n_ab = nlm_fill_weights(h_color, 2, template_size, search_size, wt_ab, cap_ab);
   *shift = nlm_shift(template_size);
@@ -389,7 +383,7 @@ extern "C" int idn_nlmeans_colored_weights(double h, double h_color, int templat
 
 extern "C" size_t idn_nlmeans_colored_workspace_size(int n, int h, int w) {
   if (n <= 0 || h <= 0 || w <= 0) return 0;
-  return ((size_t)n * h * w + 255) & ~(size_t)255;
+  return idn::align_up((size_t)n * h * w, 256);
 }
 
 extern "C" int idn_nlmeans_colored_u8(const uint8_t* src, uint8_t* dst, int n, int h, int w,
@@ -399,13 +393,10 @@ extern "C" int idn_nlmeans_colored_u8(const uint8_t* src, uint8_t* dst, int n, i
   using namespace idn;
   const char* const name = "idn_nlmeans_colored_u8";
   IDN_CHECK_ARG(src && dst && wt_l_dev && wt_ab_dev, "%s: null pointer", name);
-  IDN_CHECK_ARG(src != dst, "%s: in-place filtering is not supported (src == dst)", name);
-  IDN_CHECK_ARG(n >= 0 && h > 0 && w > 0, "%s: bad shape n=%d h=%d w=%d", name, n, h, w);
-  IDN_CHECK_ARG(row_stride >= (int64_t)w * 3, "%s: row_stride %lld < w*3", name,
-                (long long)row_stride);
-  IDN_CHECK_ARG(nlm_sizes_ok(template_size, search_size),
-                "%s: template_size must be odd in 3..7 and search_size odd in 5..21 (got %d, %d)",
-                name, template_size, search_size);
+  if (int e = check_not_in_place(name, src, dst)) return e;
+  if (int e = check_shape(name, n, h, w)) return e;
+  if (int e = check_row_stride(name, row_stride, w, 3, "3")) return e;
+  if (int e = nlm_check_sizes(name, template_size, search_size)) return e;
   const int sr = search_size / 2, b = template_size / 2 + sr;
   IDN_CHECK_ARG(h > b && w > b, "%s: image %d x %d smaller than the %d pixels the template and "
                 "search windows need", name, h, w, b + 1);
@@ -415,14 +406,13 @@ extern "C" int idn_nlmeans_colored_u8(const uint8_t* src, uint8_t* dst, int n, i
     return set_error(IDN_EUNSUPPORTED, "%s: a weight table of %d / %d entries exceeds "
                      "IDN_NLMEANS_MAX_WEIGHTS (%d): h or h_color is too large", name, n_l, n_ab,
                      IDN_NLMEANS_MAX_WEIGHTS);
-  const size_t need = idn_nlmeans_colored_workspace_size(n, h, w);
-  IDN_CHECK_ARG(need == 0 || (workspace && ws_bytes >= need), "%s: needs %zu workspace bytes "
-                "(got %zu)", name, need, workspace ? ws_bytes : (size_t)0);
+  const size_t need = idn_nlmeans_colored_workspace_size(n, h, w);  // reports 0 bytes for NULL
+  if (int e = check_workspace_got(name, workspace, workspace ? ws_bytes : 0, need, IDN_EINVAL))
+    return e;
   if (n == 0) return IDN_OK;
   const int tiles_x = (w + nlm_ow(template_size) - 1) / nlm_ow(template_size);
   const int tiles_y = (h + NLM_ROWS - 1) / NLM_ROWS;
-  if ((int64_t)n * tiles_x * tiles_y > (int64_t)INT_MAX)
-    return set_error(IDN_EUNSUPPORTED, "%s: batch too large for one launch", name);
+  if ((int64_t)n * tiles_x * tiles_y > (int64_t)INT_MAX) return batch_too_large(name);
   const unsigned grid = (unsigned)(n * tiles_x * tiles_y);
   const size_t tile = (size_t)NLM_PITCH * (NLM_ROWS + 2 * b);
   const size_t lds_l = (tile + (size_t)n_l + 1) * 4 + NLM_CBRT_BYTES;

@@ -3,6 +3,7 @@
 // This unit owns the only device memory the library keeps: the per-device inversion tables
 // (pois_tables_for).  noise.hip's noise_u8_impl reaches it through noise_poisson_launch.
 #include "noise_common.hpp"
+#include "abi_args.hpp"
 
 #include <math.h>
 
@@ -368,7 +369,7 @@ __global__ __launch_bounds__(256) void unique_mask_flat_kernel(const uint8_t* __
 
 // poisson: per-image distinct-value masks + vals, then the inversion tables (256-byte aligned)
 static size_t pois_tables_off(int n) {
-  return ((size_t)n * 9 * sizeof(uint32_t) + 255) & ~(size_t)255;
+  return idn::align_up((size_t)n * 9 * sizeof(uint32_t), 256);
 }
 extern "C" size_t idn_noise_workspace_size(int kind, int n) {
   if (kind != IDN_NOISE_POISSON || n <= 0) return 0;

@@ -33,6 +33,8 @@
 //
 // This unit holds the dispatcher, the entry points, the generic kernel and the float64 filters.
 #include "stencil_common.hpp"
+#include "abi_args.hpp"
+#include "blur_large.hpp"
 
 namespace idn {
 
@@ -193,17 +195,6 @@ static int launch_stencil(StencilOp op, const uint8_t* src, uint8_t* dst, int n,
   }
   if (rc) return rc;
   IDN_CHECK_LAUNCH(name);
-  return IDN_OK;
-}
-
-int check_filter_args(const uint8_t* src, uint8_t* dst, int n, int h, int w, int c,
-                        int64_t row_stride, const char* name) {
-  IDN_CHECK_ARG(src && dst, "%s: null pointer", name);
-  IDN_CHECK_ARG(src != dst, "%s: in-place filtering is not supported (src == dst)", name);
-  IDN_CHECK_ARG(n >= 0 && h > 0 && w > 0, "%s: bad shape n=%d h=%d w=%d", name, n, h, w);
-  IDN_CHECK_ARG(c >= 1 && c <= 4, "%s: channels must be 1..4 (got %d)", name, c);
-  IDN_CHECK_ARG(row_stride >= (int64_t)w * c, "%s: row_stride %lld < w*c", name,
-                (long long)row_stride);
   return IDN_OK;
 }
 

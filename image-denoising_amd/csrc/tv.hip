@@ -37,6 +37,7 @@
 // f32 and / or u8 = clip(rint(255 out)).  Nothing depends on timing or on the other planes of the
 // batch: a plane gives the same bits, iters included, on every call and in every batch.
 #include "idn_common.hpp"
+#include "abi_args.hpp"
 
 #include <limits.h>
 #include <math.h>
@@ -66,10 +67,11 @@ static TvLayout tv_layout(int n, int h, int w, int c) {
   L.tiles_y = (h + L.rows - 1) / L.rows;
   const size_t planes = (size_t)n * c;
   const size_t tpp = (size_t)L.tiles_x * L.tiles_y;
-  L.state = 0;
-  L.part = L.state + 2 * planes * sizeof(TvState);
-  L.dual = L.part + 2 * planes * tpp * 2 * sizeof(double);
-  L.total = L.dual + 2 * planes * (size_t)h * w * sizeof(float2);
+  Bump ws;
+  L.state = ws.take(2 * planes * sizeof(TvState));
+  L.part = ws.take(2 * planes * tpp * 2 * sizeof(double));
+  L.dual = ws.take(2 * planes * (size_t)h * w * sizeof(float2));
+  L.total = ws.total;
   return L;
 }
 
@@ -371,11 +373,8 @@ extern "C" int idn_tv_chambolle_u8(const uint8_t* src, uint8_t* dst_u8, float* d
   const char* name = "idn_tv_chambolle_u8";
   IDN_CHECK_ARG(src, "%s: null pointer (src)", name);
   IDN_CHECK_ARG(dst_u8 || dst_f32, "%s: no destination (dst_u8 and dst_f32 are both null)", name);
-  IDN_CHECK_ARG(src != dst_u8, "%s: in-place filtering is not supported (dst_u8 is src)", name);
-  IDN_CHECK_ARG(n >= 0 && h >= 1 && w >= 1, "%s: bad shape n=%d h=%d w=%d", name, n, h, w);
-  IDN_CHECK_ARG(c == 1 || c == 3, "%s: channels must be 1 or 3 (got %d)", name, c);
-  IDN_CHECK_ARG(row_stride >= (int64_t)w * c, "%s: row_stride %lld < w*c", name,
-                (long long)row_stride);
+  if (int e = check_not_in_place(name, src, dst_u8, "dst_u8 is src")) return e;
+  if (int e = check_image_1_or_3(name, n, h, w, c, row_stride)) return e;
   IDN_CHECK_ARG(isfinite(weight) && weight > 0.0, "%s: weight must be positive and finite", name);
   IDN_CHECK_ARG(isfinite(eps) && eps >= 0.0, "%s: eps must be finite and not negative", name);
   IDN_CHECK_ARG(n_iter_max >= 1 && n_iter_max <= IDN_TV_MAX_ITER,
@@ -386,11 +385,8 @@ extern "C" int idn_tv_chambolle_u8(const uint8_t* src, uint8_t* dst_u8, float* d
   const int64_t tpp = (int64_t)L.tiles_x * L.tiles_y;
   const int64_t out_tiles = ((int64_t)w * c + 255) / 256;
   if ((int64_t)w * c > INT_MAX || planes * tpp > INT_MAX || (int64_t)n * h * out_tiles > INT_MAX)
-    return set_error(IDN_EUNSUPPORTED, "%s: batch too large for one launch", name);
-  if (!workspace || ws_bytes < L.total)
-    return set_error(IDN_EWORKSPACE, "%s: workspace of %zu bytes needed, %zu given", name, L.total,
-                     workspace ? ws_bytes : (size_t)0);
-  IDN_CHECK_ARG(((uintptr_t)workspace & 7) == 0, "%s: workspace must be 8-byte aligned", name);
+    return batch_too_large(name);
+  if (int e = check_workspace(name, workspace, ws_bytes, L.total)) return e;
 
   char* base = static_cast<char*>(workspace);
   TvState* state[2];

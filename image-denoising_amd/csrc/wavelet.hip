@@ -37,6 +37,7 @@
 // Bands that only continuous arithmetic reads are stored, and where measured faster computed, in
 // fp32 (wl_fband).  DESIGN.md lists the forms of the product and of the tuning library.
 #include "wavelet_common.hpp"
+#include "abi_args.hpp"
 
 namespace idn {
 
@@ -60,7 +61,7 @@ inline WlLayout wl_layout(int n, int h, int w, int wv, int levels) {
     Lt.off_band[l] = off;
     off += (size_t)12 * Lt.H[l] * Lt.W[l];
   }
-  Lt.img_floats = (off + 63) / 64 * 64;
+  Lt.img_floats = align_up(off, 64);
   Lt.stats_off = (size_t)n * Lt.img_floats * sizeof(wreal);
   size_t tiles_tot = 0;
   for (int l = 1; l <= Lt.L && l <= WL_MAXL; ++l) {
@@ -359,9 +360,9 @@ static int wavelet_impl(const uint8_t* src, const double* in_f64,
   // pywt needs every level's input at least one sample long; skimage warns but proceeds
   for (int l = 1; l <= Lt.L; ++l)
     IDN_CHECK_ARG(Lt.H[l - 1] >= 1 && Lt.W[l - 1] >= 1, "idn_wavelet_denoise_u8: image too small");
-  if (!workspace || ws_bytes < Lt.bytes)
-    return set_error(IDN_EWORKSPACE, "idn_wavelet_denoise_u8: needs %zu workspace bytes (got %zu)",
-                     Lt.bytes, ws_bytes);
+  if (int e = check_workspace_got("idn_wavelet_denoise_u8", workspace, ws_bytes, Lt.bytes,
+                                  IDN_EWORKSPACE))
+    return e;
   const WlCall C{src, in_f64, ycc_keys, out_u8, out_f32, row_stride, (wreal*)workspace,
                  (double*)((char*)workspace + Lt.stats_off),
                  (double*)((char*)workspace + Lt.part_off), as_stream(stream)};

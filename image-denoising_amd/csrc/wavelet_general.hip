@@ -31,6 +31,7 @@
 //   synthesis     wg_synth, levels L..1, details thresholded as they are staged; level 1 fuses
 //                 the clip(s), the colour transform and the u8 / f32 stores
 #include "wavelet_common.hpp"
+#include "abi_args.hpp"
 
 namespace idn {
 
@@ -426,7 +427,7 @@ static WgLayout wg_layout(int n, int h, int w, int c, int wv, int levels) {
     Lt.off_band[l] = off;
     off += (size_t)12 * Lt.H[l] * Lt.W[l];
   }
-  Lt.img_floats = (off + 63) / 64 * 64;
+  Lt.img_floats = align_up(off, 64);
   Lt.stats_off = (size_t)Lt.n * Lt.img_floats * sizeof(wreal);
   Lt.part_per_img = 0;
   Lt.part_off = Lt.stats_off + (size_t)Lt.n * WL_STATS * sizeof(double);
@@ -510,8 +511,7 @@ extern "C" int idn_wavelet_denoise_general(const uint8_t* src, const double* in_
   const WgLayout WL = wg_layout(n, h, w, c, wavelet, levels);
   const WlLayout& Lt = WL.Lt;
   IDN_CHECK_ARG(Lt.L >= 1 && Lt.L <= WG_MAXL, "%s: levels %d out of range (1..%d)", fn, Lt.L, WG_MAXL);
-  if (!workspace || ws_bytes < Lt.bytes)
-    return set_error(IDN_EWORKSPACE, "%s: needs %zu workspace bytes (got %zu)", fn, Lt.bytes, ws_bytes);
+  if (int e = check_workspace_got(fn, workspace, ws_bytes, Lt.bytes, IDN_EWORKSPACE)) return e;
   const WlCall C{src, in_f64, nullptr, out_u8, out_f32, row_stride, (wreal*)workspace,
                  (double*)((char*)workspace + Lt.stats_off), nullptr, as_stream(stream)};
   WgCall G;

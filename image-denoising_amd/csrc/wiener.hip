@@ -29,6 +29,7 @@
 // device.  Integer sums and integer atomics: no result depends on the order of execution or on
 // the batch an image came in.
 #include "idn_common.hpp"
+#include "abi_args.hpp"
 
 #include <limits.h>
 
@@ -309,11 +310,8 @@ extern "C" int idn_wiener_u8(const uint8_t* src, uint8_t* dst_u8, double* dst_f6
   const char* name = "idn_wiener_u8";
   IDN_CHECK_ARG(src, "%s: null pointer (src)", name);
   IDN_CHECK_ARG(dst_u8 || dst_f64, "%s: both destinations are null", name);
-  IDN_CHECK_ARG(dst_u8 != src, "%s: in-place filtering is not supported (dst_u8 == src)", name);
-  IDN_CHECK_ARG(n >= 0 && h >= 1 && w >= 1, "%s: bad shape n=%d h=%d w=%d", name, n, h, w);
-  IDN_CHECK_ARG(c == 1 || c == 3, "%s: channels must be 1 or 3 (got %d)", name, c);
-  IDN_CHECK_ARG(row_stride >= (int64_t)w * c, "%s: row_stride %lld < w*c", name,
-                (long long)row_stride);
+  if (int e = check_not_in_place(name, src, dst_u8, "dst_u8 == src")) return e;
+  if (int e = check_image_1_or_3(name, n, h, w, c, row_stride)) return e;
   IDN_CHECK_ARG(kh >= 1 && kh <= WN_KMAX && (kh & 1) && kw >= 1 && kw <= WN_KMAX && (kw & 1),
                 "%s: window sides must be odd and in 1..%d (got %d x %d)", name, WN_KMAX, kh, kw);
   IDN_CHECK_ARG(border == IDN_WIENER_ZERO || border == IDN_WIENER_REFLECT101,
@@ -337,17 +335,14 @@ extern "C" int idn_wiener_u8(const uint8_t* src, uint8_t* dst_u8, double* dst_f6
   const int64_t wb = (int64_t)w * c;
   const int64_t tiles = (wb + WN_TW - 1) / WN_TW, strips = ((int64_t)h + sr - 1) / sr;
   if (wb > INT_MAX - WN_KMAX * 3 - WN_TW || (int64_t)n * tiles * strips > INT_MAX)
-    return set_error(IDN_EUNSUPPORTED, "%s: batch too large for one launch", name);
+    return batch_too_large(name);
   unsigned long long* q = nullptr;
   if (!noise) {
     if ((int64_t)h * w > WN_EST_MAX)
       return set_error(IDN_EUNSUPPORTED, "%s: the noise estimate takes planes of at most 2^28 "
                        "samples (got %d x %d)", name, h, w);
-    const size_t need = (size_t)n * c * sizeof(uint64_t);
-    if (!workspace || ws_bytes < need)
-      return set_error(IDN_EWORKSPACE, "%s: workspace of %zu bytes needed, %zu given", name, need,
-                       workspace ? ws_bytes : (size_t)0);
-    IDN_CHECK_ARG(((uintptr_t)workspace & 7) == 0, "%s: workspace must be 8-byte aligned", name);
+    if (int e = check_workspace(name, workspace, ws_bytes, idn_wiener_workspace_size(n, c)))
+      return e;
     q = static_cast<unsigned long long*>(workspace);
   }
 
