@@ -11,6 +11,15 @@
  *     h*row_stride.  f64 arrays use the same element order with pitch W*C elements.
  *   - Pointers are DEVICE pointers owned by the caller; nothing is allocated inside a call.
  *     Calls that need scratch take (workspace, ws_bytes) and expose idn_*_workspace_size().
+ *   - Workspaces (every entry point that takes one).  What the workspace holds on entry does not
+ *     matter: a call initialises what it reads, on `stream`, and gives the same bits on a zeroed
+ *     buffer, on one full of 0xFF and on what any earlier call left.  Nothing outside
+ *     [workspace, workspace + idn_*_workspace_size()) is written, whatever ws_bytes says beyond
+ *     it.  Consecutive calls on one stream, of one entry point or of different ones, may share
+ *     one buffer of the largest size; calls on two streams need a buffer each.  What a call
+ *     leaves in its workspace is unspecified but for the diagnostics documented below
+ *     (tests/test_workspace_gpu.py: exact-size guarded workspaces under three fills, the ops one
+ *     after the other on one buffer, every op on a side stream).
  *   - Every call is stream-ordered on `stream` (NULL = default stream) and capture-safe
  *     (no sync, no malloc; idn_jpeg_decode_u8 and the one-time Poisson table build are the
  *     documented exceptions).  The RNG position is explicit: Philox4x32 keyed by (seed ^ a per-
